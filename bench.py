@@ -20,12 +20,21 @@ ONE frame per step, its 32x32 buckets dealt id mod N (reference bucket grid,
 src/Scene.cpp:90-95), every rank renders its share in one launch into packed
 float tiles, one RCCL gather of the framebuffer brings them to rank 0, which
 scatters them into the frame; the gather of step k overlaps the render of
-step k + 1 (miro/tiles.py BatchPipeline).  `split_times` gives each rank's
-render and the gather alone; `weak` times a camera path of N frames per step
+step k + 1 (miro/tiles.py BatchPipeline).  With --full, `split_times` gives each
+rank's render and the gather alone; `weak` times a camera path of N frames per step
 (buckets of all N frames dealt id mod N, 8-bit tiles), i.e. weak scaling.
 
 value = rays of all frames of all steps / max-over-ranks wall time.  Rank 0
 prints one JSON line.
+
+A plain run does what the headline needs and no more: scene setup, one instrumented
+frame (the ray count of a step), clock settle, --warmup steps, --steps timed steps,
+the line (metric, value, unit, ms_per_step, config, ...).  --dump-outputs DIR also
+writes the last timed step's frame(s) as DIR/rgb.npy (float RGB, where the path
+writes it) and DIR/rgb8.npy (the 8-bit Image), float32.  --full adds every other
+measurement and check to the line: frame_check, roofline, launch_ms,
+frame_latency_ms, wave_timing_us, build, walk, split_times / weak / single_frame
+and the CPU baseline (cpu_baseline; --no-cpu-baseline leaves it out).
 """
 from __future__ import annotations
 
@@ -61,7 +70,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the timed frame checked "
+                         "against a single render, the N > 1 split's per-rank / single-frame / weak-scaling timings, "
+                         "the latency frames and per-kernel roofline figures, the build check and the CPU baseline; "
+                         "a plain run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the frame(s) a caller of the "
+                         "timed path receives: float RGB where the path writes it, and the 8-bit RGB) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (a fixed, seeded sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU oracle sample out")
     ap.add_argument("--frames", type=int, default=0, help="frames per step (default: 1 at N=1, N at N>1)")
     ap.add_argument("--settle-s", type=float, default=0.3,
                     help="untimed rendering before the warmup steps until this many seconds have passed (clock settle)")
@@ -102,7 +120,10 @@ def parse():
                     help="single frames (nothing else in flight) timed after the run for launch_ms / frame latency")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="libmrt tuning switch (mrt_set_tuning) for A/B and profiling runs; reported in the line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -182,6 +203,29 @@ def kernel_bytes(st, px, hits, float_out=True, wavefront=False):
     if wavefront:
         shade += st["shadow_rays"] * (32 + 32 + 1 + 1) + px * 2
     return primary, shade
+
+
+DUMP_BUDGET = 64 * 1000 * 1000   # --dump-outputs: bytes of all files together
+DUMP_SEED = 20111
+
+
+def dump_outputs(out_dir, arrays, shape):
+    """--dump-outputs: {name: device tensor or None} -> DIR/<name>.npy in float32 (8-bit
+    channels as their integer values), each of `shape` (frames, H, W, 3).  Where all of
+    them together would pass the budget, every file holds a seeded sample of its array's
+    elements instead: the same ascending indices in every run with the same arguments."""
+    import numpy as np
+    arrays = {k: t for k, t in arrays.items() if t is not None}
+    n = int(np.prod(shape))
+    room = (DUMP_BUDGET // len(arrays) - 4096) // 4   # float32 elements per file (4 KB for the .npy header)
+    idx = None
+    if n > room:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, room))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.reshape(-1)[:n].cpu().numpy()
+        a = a.reshape(shape) if idx is None else a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def cpu_model():
@@ -694,6 +738,13 @@ def main():
         return {"timed_frame_sha256": got, "single_frame_sha256": ref, "equal": got == ref,
                 "compared": ("float + 8-bit" if t_f is not None else "8-bit") + " RGB of the last timed step's frame"}
 
+    def dump_last(t_f, t_8):
+        """--dump-outputs: the frame(s) of the last timed step (rank 0's assembled ones at N > 1),
+        copied out before anything else renders into those buffers."""
+        if args.dump_outputs:
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"rgb": t_f, "rgb8": t_8}, (n_frames, H, W, 3))
+
     adaptive = bool(cfg.get("subdivs")) and max(cfg["subdivs"][:2]) > 1
     assemble = None
     if args.share:
@@ -712,7 +763,8 @@ def main():
         progress("timed region")
         elapsed = timed(frame_step, lambda: None, args.steps)
         last = (nstep[0] - 1) % inflight
-        frame_check = check_timed_frame(frame[last], frame8[last])
+        dump_last(frame[last], frame8[last])
+        frame_check = check_timed_frame(frame[last], frame8[last]) if args.full else None
     else:
         assemble = "gather"
         if split and args.assemble == "ipc":
@@ -729,7 +781,9 @@ def main():
             st, (shadow_total, eye_total, second_total) = count_rays(lambda: render_one(opts_count))
             elapsed = timed(pipe.step, pipe.flush, args.steps)
             last = (pipe.k - 1) % pipe.depth
-            frame_check = check_timed_frame(own[last][0], own[last][1]) if rank == 0 else None
+            if rank == 0:
+                dump_last(own[last][0], own[last][1])
+            frame_check = check_timed_frame(own[last][0], own[last][1]) if rank == 0 and args.full else None
             out_bytes_px = 3 + (12 if args.split_float else 0)
         else:
             pipe, render, items, mine, _ = make_pipe(n_frames, float_tiles=split)
@@ -739,8 +793,10 @@ def main():
             st, (shadow_total, eye_total, second_total) = count_rays(lambda: render_one(opts_count))
             elapsed = timed(pipe.step, pipe.flush, args.steps)
             last = (pipe.k - 1) % pipe.depth
+            if rank == 0:
+                dump_last(pipe.out_f[last] if split else None, pipe.out_8[last])
             frame_check = check_timed_frame(pipe.out_f[last] if split else None, pipe.out_8[last]) \
-                if rank == 0 and (n_frames == 1 or split) else None
+                if rank == 0 and args.full and (n_frames == 1 or split) else None
     shadow_mine, eye_mine, second_mine = st["shadow_rays"], (st["primary_rays"] if adaptive else 0), st["secondary_rays"]
     primary_total = eye_total if adaptive else n_frames * W * H
     rays_per_step = primary_total + shadow_total + second_total      # all frames of the batch, all ranks
@@ -750,8 +806,9 @@ def main():
     # alone: render = HIP events of one launch on this rank's stream; ipc: one frame-end
     # barrier (all-reduce of one int) between barriers, gather: one RCCL gather of the
     # tile buffer), and the weak-scaling batch of N frames per step as the secondary key
+    # (--full only, like everything below that takes a run of its own)
     split_times, weak = None, None
-    if world > 1 and split:
+    if args.full and world > 1 and split:
         r_ms, g_ms = [], []
         flag = torch.zeros(1, dtype=torch.int32, device="cuda")
         for _ in range(5):
@@ -824,8 +881,9 @@ def main():
     # per-launch durations of the uninstrumented kernels (HIP events on the
     # launch's stream), and the latency of one frame with nothing else in flight
     prim_ms, shade_ms, lat_ms = [], [], []
-    progress("latency frames")
-    for _ in range(max(1, args.latency_frames)):
+    if args.full:
+        progress("latency frames")
+    for _ in range(max(1, args.latency_frames) if args.full else 0):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if use_frame_path:
@@ -846,6 +904,64 @@ def main():
         dist.destroy_process_group()
         return
     value = rays_per_step * args.steps / elapsed / 1e6
+    # the headline line: all a plain run prints
+    out = {
+        "metric": ("Mray/s (primary+shadow) on Sponza 1920x1080" if args.config == "C3" else
+                   f"Mray/s (primary+shadow{'+secondary' if second_total else ''}) [{args.config}: {cfg['name']}]"),
+        "value": round(value, 2), "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        # N = 1 and the split: one frame per step whatever N is (total work fixed);
+        # --split batch: N frames per step (work per GPU fixed)
+        "scaling": "strong" if (world == 1 or split) else "weak", "vs_baseline": None, "dtype": "f32",
+        "data": ("the reference's own final-scene data (Models/Final, Textures, Images/sky.hdr; assets/final) with "
+                 "seeded stand-ins for the 7 meshes and the environment .tga missing from the snapshot; %d world objects, "
+                 "%d BLAS triangles" % (scene.bvh_info["prims"], getattr(scene, "blas_prims", 0))
+                 if cfg["mesh"] == "final" else
+                 "synthetic (deterministic %s stand-in, %d tris; %s.obj is not in the reference snapshot%s)"
+                 % ({"sponza": "Sponza", "sponza_large": "Sponza (262k variant)", "bunny": "bunny",
+                     "instances": "dragon_2 / buddha_smooth"}.get(cfg["mesh"], cfg["mesh"]), scene.bvh_info["prims"],
+                    {"instances": "dragon_2.obj / buddha_smooth", "sponza_large": "sponza"}.get(cfg["mesh"], cfg["mesh"]),
+                    "; Images/Arches_E_PineTree.hdr dome / environment map" if cfg.get("env") else "")),
+        "config": {"workload": cfg["name"], "config": args.config, "width": W, "height": H,
+                   "spp": 1 if not adaptive else f"adaptive {cfg['subdivs'][0]}..{cfg['subdivs'][1]} subdivs, "
+                   f"{primary_total / (n_frames * W * H):.2f} eye rays/px",
+                   "frames_per_step": n_frames, "rays_per_step": rays_per_step, "shadow_rays": shadow_total,
+                   "secondary_rays": second_total,
+                   "qbvh_nodes": scene.bvh_info["nodes"], "qbvh_leaves": scene.bvh_info["leaves"],
+                   "frames_in_flight": inflight, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                   "parallelism": "single GPU, whole frame" if use_frame_path else
+                   ((f"one {W}x{H} frame per step" if n_frames == 1 else
+                     f"batched: {n_frames} {W}x{H} frames of the camera path per step (distinct cameras), rendered "
+                     f"by each rank in ONE launch (--frames-per-launch)") +
+                    f" split over {world} GPUs: its 32x32 buckets dealt id mod {world} (src/Scene.cpp:90-174), " +
+                    ("each rank's kernel stores its pixels straight into rank 0's frames through an IPC mapping, one "
+                     "frame-end barrier (all-reduce of one int) per step, no gather or unpack"
+                     if assemble == "ipc" else
+                     "float32 tiles, one RCCL gather of the framebuffer(s) to rank 0 per step" +
+                     ("" if assemble == "gather" else f" [{assemble}]")) +
+                    f", consecutive steps pipelined over {depth} buffers" if split else
+                    f"{n_frames}-frame camera path per step, 32x32 buckets dealt id mod {world}, "
+                    f"one RCCL gather of 8-bit tiles per step (double-buffered)")},
+    }
+    # keys of both the plain and the --full line that cost no run of their own
+    # one-time host side (outside the timed region): BVH::build over the scene's triangles
+    out["scene_setup"] = _scene_setup(scene)
+    if region:
+        out["timed_region"] = region
+    if settle:   # untimed clock-settle steps before the warmup (see timed())
+        out["settle"] = settle
+    if tuning:
+        out["tuning"] = tuning
+    if rehearse:
+        out["rehearsal"] = (f"MRT_BENCH_REHEARSE=gloo: {world} ranks sharing ONE GPU, collectives over gloo through "
+                            f"host copies -- a run of the multi-rank code, not a measurement")
+    if args.dump_outputs:
+        out["dumped_outputs"] = args.dump_outputs
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     px_mine = W * H if use_frame_path else _pixels_in_frame(sorted(set(mine)), bpf, bx, W, H)
     hits_mine = hits_px
     # the specialised kernel runs for one point light, one path and no environment map
@@ -979,43 +1095,7 @@ def main():
                                     % (simd_cyc, waves))
     # primary-kernel lanes doing node work per issued wave step (adaptive: no primary launch)
     lane_util = round(st["primary_node_visits"] / (64 * st["primary_wave_steps"]), 4) if st["primary_wave_steps"] else None
-    out = {
-        "metric": ("Mray/s (primary+shadow) on Sponza 1920x1080" if args.config == "C3" else
-                   f"Mray/s (primary+shadow{'+secondary' if second_total else ''}) [{args.config}: {cfg['name']}]"),
-        "value": round(value, 2), "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        # N = 1 and the split: one frame per step whatever N is (total work fixed);
-        # --split batch: N frames per step (work per GPU fixed)
-        "scaling": "strong" if (world == 1 or split) else "weak", "vs_baseline": None, "dtype": "f32",
-        "data": ("the reference's own final-scene data (Models/Final, Textures, Images/sky.hdr; assets/final) with "
-                 "seeded stand-ins for the 7 meshes and the environment .tga missing from the snapshot; %d world objects, "
-                 "%d BLAS triangles" % (scene.bvh_info["prims"], getattr(scene, "blas_prims", 0))
-                 if cfg["mesh"] == "final" else
-                 "synthetic (deterministic %s stand-in, %d tris; %s.obj is not in the reference snapshot%s)"
-                 % ({"sponza": "Sponza", "sponza_large": "Sponza (262k variant)", "bunny": "bunny",
-                     "instances": "dragon_2 / buddha_smooth"}.get(cfg["mesh"], cfg["mesh"]), scene.bvh_info["prims"],
-                    {"instances": "dragon_2.obj / buddha_smooth", "sponza_large": "sponza"}.get(cfg["mesh"], cfg["mesh"]),
-                    "; Images/Arches_E_PineTree.hdr dome / environment map" if cfg.get("env") else "")),
-        "config": {"workload": cfg["name"], "config": args.config, "width": W, "height": H,
-                   "spp": 1 if not adaptive else f"adaptive {cfg['subdivs'][0]}..{cfg['subdivs'][1]} subdivs, "
-                   f"{primary_total / (n_frames * W * H):.2f} eye rays/px",
-                   "frames_per_step": n_frames, "rays_per_step": rays_per_step, "shadow_rays": shadow_total,
-                   "secondary_rays": second_total,
-                   "qbvh_nodes": scene.bvh_info["nodes"], "qbvh_leaves": scene.bvh_info["leaves"],
-                   "frames_in_flight": inflight, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                   "parallelism": "single GPU, whole frame" if use_frame_path else
-                   ((f"one {W}x{H} frame per step" if n_frames == 1 else
-                     f"batched: {n_frames} {W}x{H} frames of the camera path per step (distinct cameras), rendered "
-                     f"by each rank in ONE launch (--frames-per-launch)") +
-                    f" split over {world} GPUs: its 32x32 buckets dealt id mod {world} (src/Scene.cpp:90-174), " +
-                    ("each rank's kernel stores its pixels straight into rank 0's frames through an IPC mapping, one "
-                     "frame-end barrier (all-reduce of one int) per step, no gather or unpack"
-                     if assemble == "ipc" else
-                     "float32 tiles, one RCCL gather of the framebuffer(s) to rank 0 per step" +
-                     ("" if assemble == "gather" else f" [{assemble}]")) +
-                    f", consecutive steps pipelined over {depth} buffers" if split else
-                    f"{n_frames}-frame camera path per step, 32x32 buckets dealt id mod {world}, "
-                    f"one RCCL gather of 8-bit tiles per step (double-buffered)")},
+    out.update({
         # The traversal is bound by latency along each wave's dependent chain
         # (~35% VALU busy, 41% memory wait); its algorithmic bytes
         # are served by L1/L2, so the ceiling they are priced against is the L2
@@ -1034,33 +1114,22 @@ def main():
                                                                     + shadow_mine + second_mine), 3)},
         "launch_ms": {"primary": round(pm, 4), "shade": round(sm, 4)},
         "frame_latency_ms": round(float(np.median(lat_ms)), 4),
-        # one-time host side (outside the timed region): BVH::build over the scene's triangles
-        "scene_setup": _scene_setup(scene),
         # instrumented (count-mode) launch: wall-clock spread of the persistent waves
         # (null where a pass records no wave clocks: the chain engine's many launches)
         "wave_timing_us": {k: (round(st[k], 1) if 0 <= st[k] < 1e9 else None)
                            for k in ("primary_span_us", "primary_ramp_us", "primary_tail_us",
                                      "shade_span_us", "shade_ramp_us", "shade_tail_us")},
-    }
+    })
     if cfg["mesh"] == "final":   # the reference's only published absolute number is this scene's
         out["reference_published"] = {
             "render": "20 minutes on an i7 quadcore desktop (webpage/aguzman_jschwarzhaupt.html:147), 1904x1042",
             "this_frame_s": round(elapsed / args.steps, 4),
             "note": "not the same measurement: the reference frame is its CPU path on its own full assets (seven of "
                     "them, and the environment image, are stand-ins here) and a different RNG stream"}
-    if region:
-        out["timed_region"] = region
-    if settle:   # untimed clock-settle steps before the warmup (see timed())
-        out["settle"] = settle
     try:   # the library's embedded source hash against the sources beside it (tools/source_hash.py)
         out["build"] = _lib.build_info(L)
     except Exception as e:   # reported, never fatal
         out["build"] = {"error": str(e)}
-    if tuning:
-        out["tuning"] = tuning
-    if rehearse:
-        out["rehearsal"] = (f"MRT_BENCH_REHEARSE=gloo: {world} ranks sharing ONE GPU, collectives over gloo through "
-                            f"host copies -- a run of the multi-rank code, not a measurement")
     if frame_check is not None:
         out["frame_check"] = frame_check
     if st.get("fused"):   # the frame kernel's walk (LDS top nodes only with tuning lds_nodes 1)

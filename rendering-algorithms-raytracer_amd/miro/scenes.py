@@ -29,8 +29,17 @@ SPONZA_LIGHT_OBJ = os.path.join(ASSETS, "sponza-light.obj")      # Models/sponza
 SKIES = {"arches": ARCHES_HDR}
 
 
+DEFAULT_CACHE = os.path.join("/tmp", "mrt_scenes")
+
+
 def _cache_dir():
-    d = os.environ.get("MRT_SCENE_CACHE", os.path.join("/tmp", "mrt_scenes"))
+    """$MRT_SCENE_CACHE, or the shared default -- unless that one exists and belongs to
+    another user (files cannot be added to it): then this user's own beside it."""
+    d = os.environ.get("MRT_SCENE_CACHE")
+    if d is None:
+        d = DEFAULT_CACHE
+        if os.path.isdir(d) and not os.access(d, os.W_OK | os.X_OK):
+            d += "-%d" % os.getuid()
     os.makedirs(d, exist_ok=True)
     return d
 

@@ -1,5 +1,5 @@
-"""Regenerate the committed fixtures (run in the build container, where the
-reference's model files are readable at /root/reference/Models).
+"""Regenerate the committed fixtures from this repository's copies of the reference's
+model files (tests/golden/models, assets/final).
 
 Inputs: the reference's own test assets, loaded by the CPU oracle's restatement
 of TriangleMesh::loadObj (so the arrays carry the loader's x0.99999994 scaling
@@ -20,14 +20,16 @@ sys.path.insert(0, os.path.join(ROOT, "rendering-algorithms-raytracer_amd"))
 import oracle as O  # noqa: E402
 from miro import scenes  # noqa: E402
 
-MODELS = "/root/reference/Models"
+sys.path.insert(0, os.path.dirname(HERE))
+from conftest import ref_model  # noqa: E402
+
 MESHES = {"cornell_box": "cornell_box.obj", "teapot": "teapot.obj", "explosion01": "Final/explosion01.obj"}
 
 
 def load_mesh(rel):
     s = O.OracleScene()
     m = s.add_material("lambert")
-    s.add_obj(os.path.join(MODELS, rel), m)
+    s.add_obj(ref_model(rel), m)
     return s.mesh_arrays(0)
 
 

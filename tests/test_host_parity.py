@@ -1,14 +1,12 @@
 """Host side of the product (libmrt.so loader + BVH builder, no GPU needed)
 against the CPU oracle: bit-identical meshes and bit-identical QBVH arrays,
 i.e. the device traverses the hierarchy the reference would build."""
-import os
-
 import numpy as np
 import pytest
 
 import miro
 import oracle as O
-from conftest import REF_MODELS
+from conftest import ref_model
 from helpers import fixture_mesh
 from miro import scenes
 
@@ -52,21 +50,19 @@ def assert_same_bvh(p, o):
 OBJS = ["cornell_box.obj", "teapot.obj", "sphere2.obj", "Final/tree03Leaves.obj", "Final/explosion01.obj"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference models not present")
 @pytest.mark.parametrize("rel", OBJS)
 def test_loader_and_bvh_match_oracle_on_reference_models(rel):
-    path = os.path.join(REF_MODELS, rel)
+    path = ref_model(rel)
     p, o = product_scene(obj=path), oracle_scene(obj=path)
     for a, b in zip(p.mesh_arrays(0), o.mesh_arrays(0)):
         assert_bits_equal(a, b)
     assert_same_bvh(p, o)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference models not present")
 def test_loader_with_transform_matches_oracle():
     ctm = miro.Matrix4x4()
     ctm.m = np.array([[0.5, 0.1, 0.0, 1.0], [0.0, 2.0, 0.3, -2.0], [0.2, 0.0, 1.5, 0.5], [0.0, 0.0, 0.0, 1.0]], np.float32)
-    path = os.path.join(REF_MODELS, "teapot.obj")
+    path = ref_model("teapot.obj")
     p, o = product_scene(obj=path, ctm=ctm), oracle_scene(obj=path, ctm=ctm)
     for a, b in zip(p.mesh_arrays(0), o.mesh_arrays(0)):
         assert_bits_equal(a, b)
@@ -107,3 +103,22 @@ def test_empty_scene_build_fails():
     s = miro.Scene()
     with pytest.raises(miro.MRTError):
         s.preCalc()
+
+
+def test_scene_cache_dir_falls_back_when_the_shared_one_is_another_users(tmp_path, monkeypatch):
+    """MRT_SCENE_CACHE wins; without it the shared default is used while this user can add
+    files to it, and a directory of this user's own beside it when it cannot."""
+    import os
+    shared = str(tmp_path / "shared")
+    os.makedirs(shared)
+    monkeypatch.setattr(scenes, "DEFAULT_CACHE", shared)
+    monkeypatch.setenv("MRT_SCENE_CACHE", str(tmp_path / "named"))
+    assert scenes._cache_dir() == str(tmp_path / "named") and os.path.isdir(tmp_path / "named")
+    monkeypatch.delenv("MRT_SCENE_CACHE")
+    assert scenes._cache_dir() == shared
+    real = os.access
+    monkeypatch.setattr(os, "access", lambda p, mode, **kw: False if p == shared else real(p, mode, **kw))
+    own = scenes._cache_dir()
+    assert own == "%s-%d" % (shared, os.getuid()) and os.path.isdir(own)
+    monkeypatch.setattr(scenes, "DEFAULT_CACHE", str(tmp_path / "absent"))   # not there yet: created and used
+    assert scenes._cache_dir() == str(tmp_path / "absent") and os.path.isdir(tmp_path / "absent")

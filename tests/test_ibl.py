@@ -2,19 +2,16 @@
 DomeLight tables (libmrt.so host code) against the CPU oracle, and the oracle's
 decoder pinned against an independent numpy decode of the RGBE bytes (the
 reference's HDRLoader, src/hdrloader.cpp:29-190, ships no tests of its own).
-The reference's own Images/*.hdr are decoded too when present."""
-import glob
-import os
+The reference's own .hdr images that this repository holds are decoded too."""
 
 import numpy as np
 import pytest
 
 import miro
 import oracle as O
+from conftest import ref_hdr_images
 from hdr_files import HEADER, decode, rgbe_pattern, write_hdr
 from miro import scenes
-
-REF_IMAGES = "/root/reference/Images"
 
 
 def bits(a):
@@ -73,15 +70,14 @@ def test_hdr_malformed_inputs_fail_loudly(tmp_path):
         product_hdr(tmp_path / "missing.hdr")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMAGES), reason="reference images not present")
 def test_reference_hdr_images_decode_identically():
-    paths = sorted(glob.glob(os.path.join(REF_IMAGES, "*.hdr")))
+    paths = ref_hdr_images()
     assert paths
-    for p in paths:
+    for p in paths.values():
         o, q = O.hdr_load(p), product_hdr(p)
         assert np.array_equal(bits(o), bits(q)), p
         assert np.isfinite(o).all() and o.max() > 0, p
-    sky = O.hdr_load(os.path.join(REF_IMAGES, "sky.hdr"))
+    sky = O.hdr_load(paths["sky.hdr"])
     assert sky.shape == (500, 1000, 3)   # header "-Y 500 +X 1000"
 
 
@@ -115,9 +111,8 @@ def test_dome_tables_match_oracle(W, H):
     assert (p["cdf_v"][:, 0] == 0).all() and (p["cdf_v"][:, -1] == 1).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMAGES), reason="reference images not present")
 def test_dome_tables_of_reference_sky_match_oracle():
-    rgb = O.hdr_load(os.path.join(REF_IMAGES, "sky.hdr"))
+    rgb = O.hdr_load(ref_hdr_images()["sky.hdr"])
     p, o = dome_product(rgb), dome_oracle(rgb)
     for k in O.DOME_KEYS:
         assert np.array_equal(bits(p[k]), bits(o[k])), k

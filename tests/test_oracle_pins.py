@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from conftest import GOLDEN, REF_MODELS
+from conftest import GOLDEN, ref_model
 from helpers import fixture_mesh
 
 
@@ -23,12 +23,11 @@ def test_explosion01_qbvh_matches_reference_counts():
     assert info["leaves"] == 23365    # reference QBVH_Node::leafCount
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference models not present")
 @pytest.mark.parametrize("name,rel", [("cornell_box", "cornell_box.obj"), ("teapot", "teapot.obj")])
 def test_loader_fixture_reproducible(name, rel):
     s = O.OracleScene()
     m = s.add_material("lambert")
-    s.add_obj(os.path.join(REF_MODELS, rel), m)
+    s.add_obj(ref_model(rel), m)
     got = s.mesh_arrays(0)
     for a, b in zip(got, fixture_mesh(name)):
         assert np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))

@@ -5,7 +5,6 @@
 # alternated twice; then tuning A/Bs given as "CFG:key=v1,v2" words in $TUNES.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 for c in ${CONFIGS:-C3}; do for i in 1 2; do for L in ${LIBS:-libmrt libmrt_r04}; do
   echo "== $c $L run $i"
   AB_CONFIG=$c MRT_LIB=rendering-algorithms-raytracer_amd/lib/$L.so timeout -k 10 240 python tools/ab_bench.py \

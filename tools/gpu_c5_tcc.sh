@@ -6,10 +6,10 @@ set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd /tmp && export TMPDIR=/tmp
 cd "$ROOT" || exit 1
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 mkdir -p gpurun_out/c5tcc
 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv \
     -d gpurun_out/c5tcc/pmc -o run -- python3 bench.py --config C5 --inflight 1 --steps 3 --warmup 1 --no-cpu-baseline \
+    --full \
     --latency-frames 1 > gpurun_out/c5tcc/bench.log 2>&1 || exit $?
 python3 - <<'PY'
 import csv, collections, re

@@ -4,7 +4,6 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 timeout -k 10 900 python -u -m pytest tests/test_chain.py tests/test_dispersion.py tests/test_adaptive.py \
     tests/test_secondary.py tests/test_path_trace.py -x -v -m gpu --timeout 240 --timeout-method thread \
     > gpurun_out/pytest_chain.log 2>&1

@@ -3,9 +3,8 @@
 # every rank on cuda:0), then the modeled 8-GPU curves (--share) with direct writes.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 mkdir -p gpurun_out/share
-MRT_BENCH_REHEARSE=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline \
+MRT_BENCH_REHEARSE=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline \
     > gpurun_out/share/rehearse_n2.log 2>&1
 rc=$?; tail -1 gpurun_out/share/rehearse_n2.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc
 for spec in ${SPECS:-C3:1 C3:8 C4:1 C5:1}; do

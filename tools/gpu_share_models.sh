@@ -5,7 +5,6 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 CONFIGS="${CONFIGS:-C3}"
 FPL="${FPL:-1}"
 WIDTHS="${WIDTHS:-2,4,8}"

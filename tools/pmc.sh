@@ -10,7 +10,6 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd /tmp && export TMPDIR=/tmp
 cd "$ROOT" || exit 1
 mkdir -p gpurun_out/pmc
-export MRT_SCENE_CACHE=/tmp/mrt_scenes
 CONFIGS="${CONFIGS:-C3 C2 C4 D1 C5 A3 R3 P4 G3}"
 STEPS="${STEPS:-5}"
 
@@ -18,7 +17,7 @@ run() {
     local cfg="$1" name="$2"; shift 2
     echo "== $cfg $name: $*"
     timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "gpurun_out/pmc/$cfg/$name" -o run \
-        -- python3 bench.py --config "$cfg" --steps "$STEPS" --warmup 1 --no-cpu-baseline \
+        -- python3 bench.py --full --config "$cfg" --steps "$STEPS" --warmup 1 --no-cpu-baseline \
         > "gpurun_out/pmc/$cfg/$name.log" 2>&1
     local rc=$?
     tail -1 "gpurun_out/pmc/$cfg/$name.log" | cut -c1-160

@@ -117,7 +117,7 @@ def main():
         txt = "\n".join(lines) + "\n"
         print(txt)
         path = f"profiles/{a.round}_{cfg.lower()}_rocprof.txt"
-        open(path, "w").write(f"# rocprofv3 summaries: python3 bench.py --config {cfg} --steps 5 --warmup 1 "
+        open(path, "w").write(f"# rocprofv3 summaries: python3 bench.py --full --config {cfg} --steps 5 --warmup 1 "
                               f"--no-cpu-baseline (tools/pmc.sh)\n" + txt)
         if passes:
             out["configs"][cfg] = {"per_launch_hbm_bytes": passes}

@@ -47,7 +47,7 @@ PASS = {"primary_kernel": "primary", "frame1_kernel": "primary", "shade1_kernel"
 NO_COUNT_ARG = {"chain0_kernel", "chain_shade_kernel", "chain_compact_kernel", "chain_finish_kernel",
                 "chain_path_kernel", "tile_order_kernel", "chain_fold_kernel", "adapt_combine_kernel"}
 FRAME_KERNELS = ("primary_kernel", "frame1_kernel", "adaptive_kernel")
-# frames of one tools/prof_all.sh run (bench.py --inflight 1 --steps 6 --warmup 1): one
+# frames of one tools/prof_all.sh run (bench.py --full --inflight 1 --steps 6 --warmup 1): one
 # setup frame, the instrumented (count-mode) frame, 1 warmup, 6 timed, 5 latency frames
 FRAMES_TIMED, FRAMES_COUNT = 13, 1
 
@@ -249,7 +249,7 @@ def main():
         print(txt)
         path = f"profiles/{a.round}_{cfg.lower()}_rocprof.txt"
         open(path, "w").write(f"# tools/prof_all.sh: rocprofv3 --kernel-trace --stats and --pmc passes of "
-                              f"python3 bench.py --config {cfg} --inflight 1 --no-cpu-baseline\n" + txt)
+                              f"python3 bench.py --full --config {cfg} --inflight 1 --no-cpu-baseline\n" + txt)
         out["source"] = path
         allout["configs"][cfg] = out
     json.dump(allout, open(js, "w"), indent=1)

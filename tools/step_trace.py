@@ -1,6 +1,7 @@
 """Kernel-busy time of bench.py's timed region, from a rocprofv3 kernel trace of the
 driver's own command (tools/gpu_steptrace.sh: `rocprofv3 --kernel-trace --stats --
-python3 bench.py --config CFG --steps 20 --warmup 5`, frames in flight as the bench runs).
+python3 bench.py --full --config CFG --steps 20 --warmup 5`, frames in flight as the bench runs;
+--full for the line's roofline.per_step, whose launches come after the timed region).
 
 bench.py prints the timed region's host clocks (`timed_region`: CLOCK_MONOTONIC and
 CLOCK_BOOTTIME, ns); the clock whose window holds the trace's dispatches is used.  Per
@@ -89,7 +90,7 @@ def analyse(root, log, cfg):
     step_b = ps.get("algorithmic_bytes_per_step")
     u_step = union / steps / 1e6   # ms
     rec = {
-        "config": cfg, "command": b.get("_command", "bench.py --config %s --steps %d --warmup %d" % (cfg, steps, b["warmup"])),
+        "config": cfg, "command": b.get("_command", "bench.py --full --config %s --steps %d --warmup %d" % (cfg, steps, b["warmup"])),
         "clock": key, "steps": steps, "dispatches": len(sel), "dispatches_per_step": round(len(sel) / steps, 2),
         "busy_union_ms_per_step": round(u_step, 4), "ms_per_step_traced_run": round(window / steps / 1e6, 4),
         "bench_ms_per_step": b["ms_per_step"], "union_over_step": round(union / window, 4),
