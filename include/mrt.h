@@ -460,6 +460,9 @@ int mrt_scene_last_stats(const mrt_scene* s, mrt_stats* out);
  * wave a bucket batch smaller than the persistent grid is launched for), "wave_log"
  * [0]/1 (timing-only wave log, diagnostics).  Process-wide. */
 int mrt_set_tuning(const char* key, int value);
+/* The value a tuning key holds now (its default until set).  MRT_ERR_INVALID for a null
+ * or unknown key or a null value. */
+int mrt_get_tuning(const char* key, int* value);
 
 /* Diagnostics: per-wave records of the last count-mode render (count_visits = 1)
  * for launch 0 (primary rays) or 1 (shading + shadow rays): 60 x uint64 per wave

@@ -1,4 +1,4 @@
-// mrt_kernels.h -- device-side hot path (included by mrt_device.hip only).
+// mrt_kernels.h -- device-side hot path (included by the .hip translation units only).
 //
 // One lane = one pixel (or one query ray).  The traversal reproduces the
 // reference's QBVH stack order exactly (src/BVH.cpp:1128-1178): the node's
@@ -281,7 +281,7 @@ __host__ __device__ __forceinline__ int32_t leaf_child(uint32_t leaf, int count,
 }
 
 // QNode::pad[0] of a device node: its slot kinds, set on upload from the child
-// words (mrt_device.hip, upload_scene): bits 0-3 inner child, 4-7 leaf packet,
+// words (mrt_upload.hip, upload_scene): bits 0-3 inner child, 4-7 leaf packet,
 // 8-11 leaf packet with ProxyObject lanes.  One dword of the node's own line, read
 // instead of decoding the four child words in every step.
 __host__ __device__ __forceinline__ uint32_t slot_kinds(const int32_t child[4]) {
@@ -430,7 +430,7 @@ __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r
 // LN: wave-uniform visits of the hierarchy's top nodes (index < kLdsNodes, renumbered
 // breadth first on upload) read them from LDS (c.lnodes, one broadcast address)
 // instead of the scalar cache -- faster where the top levels end most rays (tuning
-// lds_nodes, off by default: mrt_device.hip).
+// lds_nodes, off by default: mrt_device.h).
 template <bool ANY, bool COUNT, bool FAST, bool INST, bool BL, bool CHECK, bool LN, bool XONE, bool OL>
 __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st, int32_t root,
                               int sp0, int32_t aoff) {

@@ -69,7 +69,7 @@ struct Instance {
     int32_t hit_base;                 // hit id of its BLAS object 0 (set by build_qbvh)
 };
 
-struct DeviceState;  // defined in mrt_device.hip
+struct DeviceState;  // defined in mrt_device.h
 
 struct Scene {
     std::vector<Mesh> meshes;

@@ -1,5 +1,5 @@
 // mrt_shader.h -- device shading code shared by the kernel translation units
-// (mrt_device.hip: frame kernels + host; mrt_rec.hip: the fused chain and
+// (mrt_device.hip: frame kernels + launches; mrt_rec.hip: the fused chain and
 // adaptive kernels; mrt_chain.hip: the wavefront chain kernels).  Included
 // after mrt_kernels.h / mrt_scene.h / mrt_texture.h inside namespace mrt.
 #pragma once

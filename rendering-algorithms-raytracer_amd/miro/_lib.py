@@ -28,7 +28,7 @@ EXPORTS = [
     "mrt_scene_set_material_sample_env", "mrt_scene_set_path_trace", "mrt_scene_prim_object",
     "mrt_image_info", "mrt_image_load", "mrt_scene_add_texture_typed", "mrt_scene_set_material_maps",
     "mrt_scene_mesh_set_texcoords", "mrt_scene_mesh_texcoords", "mrt_scene_set_mesh_motion", "mrt_scene_walk_info",
-    "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close",
+    "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close", "mrt_get_tuning",
 ]
 
 
@@ -189,6 +189,8 @@ def load():
                                   C.c_int, C.c_void_p, C.c_void_p]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
+    if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_get_tuning.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     L.mrt_debug_wave_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
     L.mrt_device_wall_clock_khz.argtypes = [C.c_void_p]
     L.mrt_hdr_info.argtypes = [C.c_char_p, _ip, _ip]

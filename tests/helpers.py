@@ -1,5 +1,7 @@
 """Shared scene builders for tests: the same scene description fed to the
 product (miro / libmrt.so) and to the CPU oracle."""
+import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -241,3 +243,22 @@ def config_scene(key, **kw):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """libmrt's process-wide tuning switches set to `knobs` for the body.  Each key's
+    value is read (mrt_get_tuning) before it is set, and put back on exit -- also when
+    the body, or a later key's set, raises."""
+    L = miro.lib()
+    before = {}
+    try:
+        for k, v in knobs.items():
+            cur = ctypes.c_int()
+            assert L.mrt_get_tuning(k.encode(), ctypes.byref(cur)) == 0, k
+            before[k] = cur.value
+            assert L.mrt_set_tuning(k.encode(), v) == 0, (k, v)
+        yield
+    finally:
+        for k, v in before.items():
+            assert L.mrt_set_tuning(k.encode(), v) == 0, (k, v)

@@ -6,6 +6,7 @@ import re
 
 import miro
 from conftest import ROOT
+from helpers import tuned
 from miro import _lib
 
 
@@ -37,7 +38,7 @@ def test_chain_tuning_keys_validate():
     headroom percentage in range, the scratch budget in range; bad values are
     rejected with an error, not clamped."""
     L = miro.lib()
-    try:
+    with tuned(chain_est=0, chain_est_pct=150, bin_inst=2):   # the keys set below: put back on exit
         assert L.mrt_set_tuning(b"chain_est", 0) == 0
         assert L.mrt_set_tuning(b"chain_est", 1) == 0
         assert L.mrt_set_tuning(b"chain_est_pct", 0) != 0
@@ -46,21 +47,15 @@ def test_chain_tuning_keys_validate():
         assert L.mrt_set_tuning(b"chain_mb", 0) != 0
         assert L.mrt_set_tuning(b"bin_inst", 3) != 0
         assert L.mrt_set_tuning(b"bin_inst", 2) == 0
-    finally:
-        assert L.mrt_set_tuning(b"chain_est_pct", 125) == 0
-        assert L.mrt_set_tuning(b"bin_inst", 0) == 0
-        assert L.mrt_set_tuning(b"chain_est", 1) == 0
 
 
 def test_batch_tiles_per_wave_key_validates():
     """batch_tpw (tiles per wave a bucket-batch launch is sized for): 1..64, bad values rejected."""
     L = miro.lib()
-    try:
+    with tuned(batch_tpw=1):   # put back on exit
         assert L.mrt_set_tuning(b"batch_tpw", 0) != 0
         assert L.mrt_set_tuning(b"batch_tpw", 65) != 0
         assert L.mrt_set_tuning(b"batch_tpw", 1) == 0
-    finally:
-        assert L.mrt_set_tuning(b"batch_tpw", 2) == 0
 
 
 def test_walk_tuning_keys_validate():
@@ -69,7 +64,7 @@ def test_walk_tuning_keys_validate():
     (0 / 1), scalar_nodes (bit mask 0..7); bad values rejected with an error; the walk info
     entry rejects a null scene."""
     L = miro.lib()
-    try:
+    with tuned(walk_exit=0, walk_latch=0, lds_nodes=0, scalar_nodes=0):   # the keys set below: put back on exit
         for k, good, bad in ((b"walk_exit", (0, 1), (-1, 2)), (b"walk_latch", (0, 1), (-1, 2)),
                              (b"lds_nodes", (0, 1), (-1, 2)),
                              (b"scalar_nodes", (0, 7), (-1, 8))):
@@ -78,6 +73,3 @@ def test_walk_tuning_keys_validate():
             for v in bad:
                 assert L.mrt_set_tuning(k, v) != 0, (k, v)
         assert L.mrt_scene_walk_info(None, None, None) != 0
-    finally:
-        for k, v in ((b"walk_exit", 1), (b"walk_latch", 1), (b"lds_nodes", 0), (b"scalar_nodes", 7)):
-            assert L.mrt_set_tuning(k, v) == 0

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import miro
-from helpers import bits, camera, config_scene, fixture_mesh, scene_pair
+from helpers import bits, camera, config_scene, fixture_mesh, scene_pair, tuned
 from miro import scenes
 
 
@@ -188,16 +188,12 @@ def test_adaptive_pixel_refill_equals_tile_schedule(refill):
     cfg = dict(scenes.CONFIGS["C1"])
     cfg["material"] = dict(kind="blinn", kd=(0.7, 0.6, 0.5), specExp=12.0, specAmt=0.3)
     P, _, cam = scene_pair(cfg, meshes=[fixture_mesh("cornell_box")], lights=lights, subdivs=(1, 4, 0.004))
-    L = miro.lib()
-    try:
-        assert L.mrt_set_tuning(b"adapt_refill", 0) == 0
+    with tuned(adapt_refill=0):
         img0, hits0 = gpu_render(P, cam, 97, 61)
         st0 = P.last_stats
-        assert L.mrt_set_tuning(b"adapt_refill", refill) == 0
+    with tuned(adapt_refill=refill):
         img1, hits1 = gpu_render(P, cam, 97, 61)
         st1 = P.last_stats
-    finally:
-        L.mrt_set_tuning(b"adapt_refill", 32)
     assert np.array_equal(hits0["prim"], hits1["prim"])
     assert np.array_equal(bits(img0.rgb), bits(img1.rgb))
     assert np.array_equal(img0.pixels, img1.pixels)

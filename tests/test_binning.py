@@ -8,18 +8,8 @@ import numpy as np
 import pytest
 
 import miro
-from helpers import bits, camera, config_scene
+from helpers import bits, camera, config_scene, tuned
 from test_chain import CASES
-
-KNOB_DEFAULTS = dict(bin=-1, bin_dbits=2, bin_obits=2, dome_replay=1, chain=1, chain_mb=8192, chain_bands=-1,
-                     shadow_sched=-1, bin_inst=0, primary_inst_waves=5)
-
-
-def tuned(**knobs):
-    L = miro.lib()
-    for k, v in knobs.items():
-        assert L.mrt_set_tuning(k.encode(), v) == 0, k
-
 
 def render(P, cam, W, H):
     img = miro.Image()
@@ -30,12 +20,9 @@ def render(P, cam, W, H):
 
 def runs(P, cam, W, H, variants):
     out = []
-    try:
-        for v in variants:
-            tuned(**dict(KNOB_DEFAULTS, **v))
+    for v in variants:   # each on top of the defaults: tuned() puts the last variant's knobs back
+        with tuned(**v):
             out.append(render(P, cam, W, H))
-    finally:
-        tuned(**KNOB_DEFAULTS)
     return out
 
 
@@ -53,7 +40,7 @@ def test_bin_tuning_validates_key_bits():
     """Each key field has its range; the pair (2 dbits + 3 obits <= 12 bits, the
     LDS counting sort) is checked when a batch is binned."""
     L = miro.lib()
-    try:
+    with tuned(bin_dbits=6, bin_obits=0, dome_replay=0):   # the accepted values below: put back on exit
         assert L.mrt_set_tuning(b"bin", 8) != 0
         assert L.mrt_set_tuning(b"bin", -2) != 0
         assert L.mrt_set_tuning(b"bin_dbits", 7) != 0
@@ -61,10 +48,6 @@ def test_bin_tuning_validates_key_bits():
         assert L.mrt_set_tuning(b"bin_dbits", 6) == 0
         assert L.mrt_set_tuning(b"bin_obits", 0) == 0
         assert L.mrt_set_tuning(b"dome_replay", 0) == 0
-    finally:
-        assert L.mrt_set_tuning(b"bin_obits", 2) == 0
-        assert L.mrt_set_tuning(b"bin_dbits", 2) == 0
-        assert L.mrt_set_tuning(b"dome_replay", 1) == 0
 
 
 @pytest.mark.gpu

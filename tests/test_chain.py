@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import miro
-from helpers import bits, camera, config_scene, fixture_mesh, scene_pair
+from helpers import bits, camera, config_scene, fixture_mesh, scene_pair, tuned
 from miro import _lib, scenes
 
 pytestmark = pytest.mark.gpu
@@ -66,12 +66,6 @@ def need_gpu():
         pytest.fail("no HIP device visible (GPU tests must run on the MI355X box)")
 
 
-def tuned(**knobs):
-    L = miro.lib()
-    for k, v in knobs.items():
-        assert L.mrt_set_tuning(k.encode(), v) == 0, k
-
-
 def render(P, cam, W, H):
     img = miro.Image()
     img.resize(W, H)
@@ -80,13 +74,10 @@ def render(P, cam, W, H):
 
 
 def both_engines(P, cam, W, H):
-    try:
-        tuned(chain=0)
+    with tuned(chain=0):
         fused = render(P, cam, W, H)
-        tuned(chain=1)
+    with tuned(chain=1):
         chain = render(P, cam, W, H)
-    finally:
-        tuned(chain=1, chain_mb=8192)
     return fused, chain
 
 
@@ -155,11 +146,8 @@ def test_chain_tree_and_adaptive_chunks_equal_one_chunk(case):
     chunks of units per pass) equal the one-chunk frame."""
     P, _, cam = CASES[case]()
     one = render(P, cam, 48, 40)
-    try:
-        tuned(chain_mb=2)
+    with tuned(chain_mb=2):
         many = render(P, cam, 48, 40)
-    finally:
-        tuned(chain_mb=8192)
     assert_same(one, many)
 
 
@@ -170,18 +158,15 @@ def test_chain_estimated_capacities_and_fallback_equal_worst_case(case):
     and the fallback (the fused chain shading over the chunk's units) must give the
     same frame and ray counts -- in one chunk and in many."""
     P, _, cam = CASES[case]()
-    try:
-        tuned(chain_est=0)
+    with tuned(chain_est=0):
         worst = render(P, cam, 48, 40)
-        tuned(chain_est=1)
+    with tuned(chain_est=1):
         render(P, cam, 48, 40)           # seeds this stream's estimates
         est = render(P, cam, 48, 40)
-        tuned(chain_est_pct=1)
-        fb = render(P, cam, 48, 40)
-        tuned(chain_mb=2)
-        fb_many = render(P, cam, 48, 40)
-    finally:
-        tuned(chain_est=1, chain_est_pct=125, chain_mb=8192)
+        with tuned(chain_est_pct=1):
+            fb = render(P, cam, 48, 40)
+            with tuned(chain_mb=2):
+                fb_many = render(P, cam, 48, 40)
     assert worst[2]["chain_fallbacks"] == 0 and est[2]["chain_fallbacks"] == 0
     assert fb[2]["chain_fallbacks"] >= 1 and fb_many[2]["chain_fallbacks"] >= 1
     for other in (est, fb, fb_many):
@@ -205,11 +190,8 @@ def test_chain_chunks_equal_one_chunk():
     """A 1-MB scratch budget forces one chunk per few work items."""
     P, _, cam = cornell(MIXED, lights=[RECT, POINT], num_paths=2)
     one = render(P, cam, 70, 50)
-    try:
-        tuned(chain_mb=1)
+    with tuned(chain_mb=1):
         many = render(P, cam, 70, 50)
-    finally:
-        tuned(chain_mb=8192)
     assert_same(one, many)
 
 

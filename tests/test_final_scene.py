@@ -19,10 +19,8 @@ import numpy as np
 import pytest
 
 import miro
-from helpers import bits, camera, final_scene_pair
+from helpers import bits, camera, final_scene_pair, tuned
 from miro import final_scene as F
-
-CHAIN_SHADOW_STEP_DEFAULT = 0   # libmrt's default (csrc/mrt_device.hip g_chain_shadow_step)
 
 
 def test_packed_data_matches_manifest():
@@ -117,18 +115,12 @@ def test_final_scene_chain_shadow_schedules_give_identical_frames():
     if miro.device_count() < 1:
         pytest.skip("no HIP device")
     P, _, cam = final_scene_pair()
-    L = miro.lib()
     out = []
-    try:
-        for refill, step in ((0, 0), (1, 0), (0, 1)):
-            assert L.mrt_set_tuning(b"chain_shadow_refill", refill) == 0
-            assert L.mrt_set_tuning(b"chain_shadow_step", step) == 0
+    for refill, step in ((0, 0), (1, 0), (0, 1)):
+        with tuned(chain_shadow_refill=refill, chain_shadow_step=step):
             img = miro.Image(); img.resize(72, 40)
             hits = P.raytraceImage(camera(cam), img, want_hits=True)
             out.append((img, hits, dict(P.last_stats)))
-    finally:
-        L.mrt_set_tuning(b"chain_shadow_refill", 0)
-        L.mrt_set_tuning(b"chain_shadow_step", CHAIN_SHADOW_STEP_DEFAULT)
     a, ha, sa = out[0]
     for b, hb, sb in out[1:]:
         assert np.array_equal(ha["prim"], hb["prim"])

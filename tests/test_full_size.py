@@ -17,7 +17,7 @@ import pytest
 import miro
 import oracle as O
 from miro import _lib
-from helpers import bits, camera, config_scene
+from helpers import bits, camera, config_scene, tuned
 
 
 def need_gpu():
@@ -43,15 +43,8 @@ def test_full_size_frame_matches_oracle(key):
     from miro import scenes
     W, H = scenes.CONFIGS[key]["W"], scenes.CONFIGS[key]["H"]
     img = miro.Image(); img.resize(W, H)
-    tune = scenes.CONFIGS[key].get("tune", {})
-    L = miro.lib()
-    try:
-        for k, v in tune.items():
-            assert L.mrt_set_tuning(k.encode(), v) == 0
+    with tuned(**scenes.CONFIGS[key].get("tune", {})):
         hits = P.raytraceImage(camera(cam), img, want_hits=True)
-    finally:
-        for k in tune:
-            assert L.mrt_set_tuning(k.encode(), {"walk_latch": 1, "frame1_waves": 7}[k]) == 0   # the defaults
     ref = Osc.render(cam, W, H, threads=16, libm=O.LIBM_FLOAT)
     assert np.array_equal(hits["prim"], ref["hits"]["prim"]), f"{key}: primary hit ids differ"
     hit = ref["hits"]["prim"] >= 0

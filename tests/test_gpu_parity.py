@@ -11,7 +11,7 @@ import pytest
 import miro
 import oracle as O
 from conftest import GOLDEN
-from helpers import bits, camera, config_scene, fixture_mesh, scene_pair
+from helpers import bits, camera, config_scene, fixture_mesh, scene_pair, tuned
 from miro import scenes
 
 pytestmark = pytest.mark.gpu
@@ -172,10 +172,7 @@ def test_every_kernel_path_is_exact(knobs):
     """Performance switches must not change a single bit (fused vs split shading,
     one-launch frame1_kernel vs primary + shade1 launches, hardware vs select box
     test, XCD schedule, occupancy build, the walk loop's exit form and latches)."""
-    L = miro.lib()
-    try:
-        for k, v in knobs.items():
-            assert L.mrt_set_tuning(k.encode(), v) == 0
+    with tuned(**knobs):
         P, Osc, cam = config_scene("C2")
         img, hits = render(P, cam, 160, 120)
         ref = Osc.render(cam, 160, 120, threads=8)
@@ -185,10 +182,6 @@ def test_every_kernel_path_is_exact(knobs):
         assert P.last_stats["primary_leaf_visits"] == ref["primary_leaf_visits"]
         assert np.array_equal(hits["prim"], ref["hits"]["prim"])
         assert P.last_stats["shadow_rays"] == ref["shadow_rays"]
-    finally:
-        for k, v in dict(shade1=1, fast_box=1, sched=2, primary_waves=7, scalar_nodes=7, wavefront=1, fused=1,
-                         frame1_waves=7, walk_exit=1, walk_latch=1, lds_nodes=0).items():   # the library's defaults
-            L.mrt_set_tuning(k.encode(), v)
 
 
 @pytest.mark.parametrize("kind,paths", [("lambert", 1), ("blinn", 1), ("blinn", 3), ("lambert", 2)])
@@ -376,17 +369,11 @@ def shadow_schedules(P, cam, W, H):
     the any-hit answers -- and so every bit of the frame and the ray counts -- must
     not depend on the schedule, the visit order or the deferred instance walks of
     the lane-refill step."""
-    L = miro.lib()
     out = []
-    try:
-        for sched, near in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1)):   # near: nearest hit child first
-            assert L.mrt_set_tuning(b"shadow_sched", sched) == 0
-            assert L.mrt_set_tuning(b"near_first", near) == 0
+    for sched, near in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1)):   # near: nearest hit child first
+        with tuned(shadow_sched=sched, near_first=near):
             img, hits = render(P, cam, W, H)
             out.append((img, hits, P.last_stats))
-    finally:
-        L.mrt_set_tuning(b"shadow_sched", -1)
-        L.mrt_set_tuning(b"near_first", -1)
     img0, hits0, st0 = out[0]
     for img, hits, st in out[1:]:
         assert np.array_equal(hits0["prim"], hits["prim"])
@@ -407,17 +394,13 @@ def test_wavefront_shadow_pass_equals_fused_kernel(key, W, H):
     """Kernel 2a/2b/2c (shadow rays written, traced any-hit in a separate launch,
     shading resolved) against the fused shading kernel: every bit of RGB, hits and
     the shadow-ray count, in frame mode and through the batched bucket path."""
-    L = miro.lib()
     P, _, cam = config_scene(key)
-    try:
-        assert L.mrt_set_tuning(b"wavefront", 0) == 0
+    with tuned(wavefront=0):
         img0, hits0 = render(P, cam, W, H)
         st0 = P.last_stats
-        assert L.mrt_set_tuning(b"wavefront", 1) == 0
+    with tuned(wavefront=1):
         img1, hits1 = render(P, cam, W, H)
         st1 = P.last_stats
-    finally:
-        L.mrt_set_tuning(b"wavefront", 1)
     assert np.array_equal(hits0["prim"], hits1["prim"])
     assert np.array_equal(bits(img0.rgb), bits(img1.rgb))
     assert np.array_equal(img0.pixels, img1.pixels)
@@ -446,16 +429,13 @@ def test_batch_grid_sizing_gives_identical_tiles(rect):
     L = miro.lib()
     stream = torch.cuda.current_stream().cuda_stream
     out = []
-    try:
-        for tpw in (1, 2, 4, 64):
-            assert L.mrt_set_tuning(b"batch_tpw", tpw) == 0
+    for tpw in (1, 2, 4, 64):
+        with tuned(batch_tpw=tpw):
             tiles = torch.zeros(len(mine) * 1024 * 3, dtype=torch.float32, device="cuda")
             _lib.check(L.mrt_render_batch_async(P.handle, camc, 1, C.byref(opts), ids.data_ptr(), len(mine),
                                                 tiles.data_ptr(), None, stream), "batch")
             torch.cuda.synchronize()
             out.append(tiles.cpu().numpy())
-    finally:
-        assert L.mrt_set_tuning(b"batch_tpw", 2) == 0
     assert np.abs(out[0]).sum() > 0
     for o in out[1:]:
         assert np.array_equal(bits(o), bits(out[0]))

@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 import miro
-from helpers import bits, camera, fixture_mesh, scene_pair
+from helpers import bits, camera, fixture_mesh, scene_pair, tuned
 from miro import scenes
 
 RECT = dict(type="rect", v1=(2.0, 5.4, -2.0), v2=(3.5, 5.4, -2.0), v3=(2.0, 5.4, -3.5), power=15.0, samples=3,
@@ -222,9 +222,7 @@ def test_material_env_maps_match_oracle(chain):
     mirror = dict(kind="blinn", kd=(0.2, 0.2, 0.2), reflectAmt=0.9, ior=1.5, env=dict(sky=(32, 16), exposure=2.0))
     glass = dict(GLASS_PANE, refractAmt=0.9, env=dict(sky=(48, 24), exposure=0.5))
     cfg = dict(scenes.CONFIGS["C1"], material=mirror)
-    L = miro.lib()
-    try:
-        assert L.mrt_set_tuning(b"chain", chain) == 0
+    with tuned(chain=chain):
         P, O_, cam = scene_pair(dict(cfg, env=dict(sky=(64, 32), exposure=0.7)), meshes=[fixture_mesh("cornell_box")],
                                 extra=[(pane(y=2.0), glass)], num_paths=2)
         ref = assert_same(P, O_, cam, 64, 48)
@@ -234,5 +232,3 @@ def test_material_env_maps_match_oracle(chain):
         P, O_, cam = scene_pair(dict(cfg, material=diffuse, env=dict(sky=(64, 32), exposure=1.0)),
                                 meshes=[fixture_mesh("cornell_box")], path_trace=(3, True), num_paths=2)
         assert_same(P, O_, cam, 48, 36)
-    finally:
-        L.mrt_set_tuning(b"chain", 1)
