@@ -68,7 +68,7 @@ __device__ __forceinline__ v3 shade1_hit(const RenderParams& P, const Trav& T, T
             const DRay sr = make_ray(from, L);
             DHit sh{distance, 0.f, 0.f, -1};
             shadow_total++;
-            if (traverse<true, COUNT, FAST, false, true, WALK == 2, WALK != 0>(T, sr, 0.001f, sh, st)) attenuate = 0.0f;
+            if (traverse<true, COUNT, FAST, false, true, WALK == 2, WALK != 0, false, true>(T, sr, 0.001f, sh, st)) attenuate = 0.0f;
         }
         attenuate *= nDotL;
         spec = rdl * attenuate;
@@ -148,6 +148,7 @@ __global__ void __launch_bounds__(kWG, MINW) shade1_kernel(RenderParams P) {
 // WALK (traverse_impl): 0 the walk loop with a second exit (stack overflow returns), 1 one
 // exit (XONE), 2 one exit + LN, 3 one exit and one latch (OL) for the camera rays' walk.
 // Same bits either way; the host runs 3 unless tuned (walk_exit, walk_latch, lds_nodes).
+// Both walks fetch wave-uniform nodes through the wave's octant rows (traverse_impl, OROWS).
 template <bool COUNT, bool FAST, int MINW, bool POW, int WALK = 1>
 __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
     constexpr bool LN = WALK == 2;
@@ -187,7 +188,7 @@ __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
             const EyeRay er = camera_ray(PA.cam[f], PA.seed + (uint32_t)f, x, y, rsqT);
             const DRay r = make_ray(er.o, er.d);
             DHit h{1e12f, 0.f, 0.f, -1};
-            const bool hit = traverse<false, COUNT, FAST, false, true, LN, WALK != 0, WALK == 3>(T, r, 0.001f, h, st);
+            const bool hit = traverse<false, COUNT, FAST, false, true, LN, WALK != 0, WALK == 3, true>(T, r, 0.001f, h, st);
             const RenderParams& PB = reload_params();   // shading parameters
             v3 col = mk(PB.bg[0], PB.bg[1], PB.bg[2]);
             if (hit) {

@@ -218,6 +218,32 @@ __device__ __forceinline__ int box_test_oct(const float4* bx, const DRay& r, flo
     }
     return m;
 }
+// The near / far plane rows of a node's box block for the octant s (wave-uniform; 8, a mixed
+// wave: the block's own order): float offsets from the node's start, formed once per walk.  A
+// scalar node fetch reads its six rows through them, so one box_test_oct<0> body serves all
+// eight octants and no step chooses between eight copies of it.
+struct OctRows {
+    uint32_t nx, ny, nz, fx, fy, fz;
+};
+__device__ __forceinline__ OctRows oct_rows(int s) {
+    OctRows o;
+    o.nx = (s & 1) ? 12u : 0u; o.fx = 12u - o.nx;
+    o.ny = (s & 2) ? 16u : 4u; o.fy = 20u - o.ny;
+    o.nz = (s & 4) ? 20u : 8u; o.fz = 28u - o.nz;
+    return o;
+}
+// A scalar-fetched node's six rows, whole and fetched where they are read: unpinned, the
+// compiler sinks the words of slots 2 and 3 into the branches that skip an empty slot's test,
+// as single-dword loads behind address adds.
+__device__ __forceinline__ void pin_rows(float4 (&bx)[6]) {
+    typedef float f4 __attribute__((ext_vector_type(4)));   // one operand per row: the load's own SGPR quad
+    f4 v[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) v[k] = f4{bx[k].x, bx[k].y, bx[k].z, bx[k].w};
+    asm volatile("" : "+s"(v[0]), "+s"(v[1]), "+s"(v[2]), "+s"(v[3]), "+s"(v[4]), "+s"(v[5]));
+#pragma unroll
+    for (int k = 0; k < 6; k++) bx[k] = make_float4(v[k].x, v[k].y, v[k].z, v[k].w);
+}
 // box_test_fast, or box_test_oct when the wave's rays share one octant (s < 8, wave-uniform)
 __device__ __forceinline__ int box_test_sel(const float4* bx, const DRay& r, float tMin, float tMax, int s,
                                             int present = 15) {
@@ -371,8 +397,10 @@ __device__ __forceinline__ bool tri_test_lane(const Trav& c, uint32_t leaf, int 
                                               float tBest, float& t, float& a, float& b) {
     int ok;
     const uint32_t key = (leaf << 2) | (uint32_t)k;
-    const uint32_t k0 = __builtin_amdgcn_readfirstlane(key);
-    if ((c.scalar_nodes & 2) && __ballot(key != k0) == 0) {
+    // (scalar fetches switched off: bit 31, which no key has -- a leaf index has 28 bits -- makes
+    // every lane differ, so the switch costs one scalar op here, not a test and a branch)
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane(key) ^ ((c.scalar_nodes & 2) ? 0u : 0x80000000u);
+    if (__ballot(key != k0) == 0) {
         typedef const __attribute__((address_space(4))) float cfloat;
         cfloat* q = (cfloat*)(const void*)(c.leaves[k0 >> 2].tri[k0 & 3]);
         float T[9];
@@ -388,7 +416,7 @@ __device__ __forceinline__ bool tri_test_lane(const Trav& c, uint32_t leaf, int 
 }
 
 template <bool ANY, bool COUNT, bool FAST, bool INST = false, bool BL = false, bool CHECK = true, bool LN = false,
-          bool XONE = true, bool OL = false>
+          bool XONE = true, bool OL = false, bool OROWS = false>
 __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st, int32_t root = 0,
                               int sp0 = 0, int32_t aoff = 0);
 
@@ -410,6 +438,10 @@ __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r
 // BVH::intersect, QBVH branch (src/BVH.cpp:1128-1178).  Returns hit; h.prim is
 // then the packed triangle slot (leaf << 2 | k), resolved by traverse().  On a
 // stack overflow st.overflow is set and the query is abandoned.
+// The caller enters with h.prim == -1: a closest-hit walk keeps no hit flag (a
+// loop-carried bool is a lane mask, re-formed at every merge point of the two
+// divergent loops on the scalar unit); every accept stores a packed slot >= 0
+// (slot 0 is leaf 0, triangle 0), so the walk's answer is h.prim >= 0.
 //
 // Per popped node: the 4-slot box mask (branch-free); hit inner slots other
 // than the highest are pushed in slot order (branch-free LDS writes, so the
@@ -431,15 +463,23 @@ __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r
 // breadth first on upload) read them from LDS (c.lnodes, one broadcast address)
 // instead of the scalar cache -- faster where the top levels end most rays (tuning
 // lds_nodes, off by default: mrt_device.h).
-template <bool ANY, bool COUNT, bool FAST, bool INST, bool BL, bool CHECK, bool LN, bool XONE, bool OL>
+// OROWS: a wave whose rays share an octant fetches a wave-uniform node's six box rows
+// in near / far order through per-walk row offsets (oct_rows), so its scalar-node step
+// runs the one box_test_oct<0> body without choosing among the octants' copies; waves
+// of mixed octants test the node as it lies.  frame1_kernel's walks only: in the shader
+// kernels (Shader::occluded) the fetched rows are not all in scalar registers, which
+// pin_rows needs (the compiler rejects it there), so the other walks keep the per-step choice.
+template <bool ANY, bool COUNT, bool FAST, bool INST, bool BL, bool CHECK, bool LN, bool XONE, bool OL, bool OROWS>
 __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st, int32_t root,
                               int sp0, int32_t aoff) {
     int sp = sp0;
     int32_t cur = root;
-    bool hit = false;
     // octant-ordered box tests (box_test_oct) when every active lane's ray has the same
     // direction signs: most primary tiles and point-light shadow rays
     const int soct = (FAST && !(ANY && c.near_first) && (c.scalar_nodes & 4)) ? wave_octant(r) : 8;
+    // scalar node fetches of such a wave read the rows in its near / far order (oct_rows)
+    const bool orows = OROWS && FAST && (c.scalar_nodes & 1) && soct < 8;
+    const OctRows rows = oct_rows(soct);
     while (true) {
         // stack top read at the start of the step: the LDS latency overlaps the
         // node fetch and box test (used only if this step pops)
@@ -461,9 +501,33 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
             for (int k = 0; k < 6; k++) bx[k] = make_float4(nd.box[4 * k], nd.box[4 * k + 1], nd.box[4 * k + 2], nd.box[4 * k + 3]);
             m = (ANY && c.near_first) ? box_test_fast_t(bx, r, tMin, h.t, tn) : box_test_sel(bx, r, tMin, h.t, soct);
             asm volatile("; mrt: lds node" : "+v"(m));
+        } else if (orows && __ballot(cur != c0) == 0) {
+            // constant address space + uniform address -> s_load_dwordx4 per row, each through
+            // its per-walk offset (node data is read-only for the whole launch)
+            typedef const __attribute__((address_space(4))) float cfloat;
+            typedef const __attribute__((address_space(4))) int32_t cint;
+            cfloat* q = (cfloat*)(const void*)(c.nodes + c0);
+            cint* qc = (cint*)(q + 24);
+            ch = make_int4(qc[0], qc[1], qc[2], qc[3]);
+            kinds = qc[4];
+            const uint32_t ro[6] = {rows.nx, rows.ny, rows.nz, rows.fx, rows.fy, rows.fz};
+            float4 bx[6];   // near x, y, z, far x, y, z
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                cfloat* qr = q + ro[k];
+                bx[k] = make_float4(qr[0], qr[1], qr[2], qr[3]);
+            }
+            pin_rows(bx);
+            // the node's occupied slots (SGPR): its empty trailing slots are not tested
+            const int present = __builtin_amdgcn_readfirstlane((kinds | (kinds >> 4)) & 15);
+            m = box_test_oct<0>(bx, r, tMin, h.t, present);
+            // distinct markers end the branches, so the compiler cannot sink their
+            // identical box tests into one block fed by 24 v_mov copies of the SGPR node:
+            // this branch reads the boxes straight from SGPRs
+            asm volatile("; mrt: scalar node" : "+v"(m));
         } else if (FAST && (c.scalar_nodes & 1) && __ballot(cur != c0) == 0) {
-            // constant address space + uniform address -> s_load_dwordx16 (node
-            // data is read-only for the whole launch)
+            // the node as it lies (s_load_dwordx16): OROWS walks' waves of mixed octants and
+            // near-first walks; every wave of the other walks, which choose the test per step
             typedef const __attribute__((address_space(4))) float cfloat;
             typedef const __attribute__((address_space(4))) int32_t cint;
             cfloat* q = (cfloat*)(const void*)(c.nodes + c0);
@@ -473,15 +537,13 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
             float4 bx[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) bx[k] = make_float4(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]);
-            // the node's occupied slots (SGPR): its empty trailing slots are not tested
+            if (OROWS) pin_rows(bx);
             const int present = __builtin_amdgcn_readfirstlane((kinds | (kinds >> 4)) & 15);
             // (the near-first test keeps all four: skipping measured 3% slower on D1's dome shadows)
             m = (ANY && c.near_first) ? box_test_fast_t(bx, r, tMin, h.t, tn)
+                : OROWS               ? box_test_fast(bx, r, tMin, h.t, present)
                                       : box_test_sel(bx, r, tMin, h.t, soct, present);
-            // distinct markers end the two branches, so the compiler cannot sink their
-            // identical box tests into one block fed by 24 v_mov copies of the SGPR node:
-            // this branch reads the boxes straight from SGPRs
-            asm volatile("; mrt: scalar node" : "+v"(m));
+            asm volatile("; mrt: scalar node, any octant" : "+v"(m));
         } else {
             const float4* q = reinterpret_cast<const float4*>(c.nodes + cur);
             ch = reinterpret_cast<const int4*>(q)[6];
@@ -496,14 +558,16 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
         }
         const int inner = m & kinds_inner(kinds);
         int lm = m & kinds_leaf(kinds);
-        bool have_next = false;
-        int32_t nxt = 0;
+        // the lane's next node when it descends (a hit inner child: >= 0), else -1: it pops.  One
+        // integer, not a flag beside it: a loop-carried bool is a lane mask that every merge
+        // point of the divergent loop re-forms on the scalar unit
+        int32_t nxt = -1;
         if (inner) {
             // next: the highest hit slot (the reference's order); an any-hit walk in
             // near-first mode takes the nearest instead (its answer is order-free)
             const int top = (FAST && ANY && c.near_first) ? nearest_slot(inner, tn) : 31 - __builtin_clz((unsigned)inner);
             const int rest = inner ^ (1 << top);
-            bool ovf = false;
+            nxt = sel4(ch, top);
             if (rest) {
                 if (sp + 4 <= kLdsStack) {
                     c.lds[sp * kWG] = ch.x; sp += rest & 1;
@@ -522,16 +586,15 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                     // tuning walk_exit 0 (round 6: the bunny scenes' tail effect)
                     if (!pushed) {
                         st.overflow = true;
-                        if (!XONE) return hit;
+                        if (!XONE) return !ANY && h.prim >= 0;
                         sp = sp0;
-                        ovf = true;
+                        nxt = -1;
                     }
                 }
                 if (COUNT && sp > st.max_sp) st.max_sp = sp;
             }
-            nxt = sel4(ch, top);
-            have_next = !ovf;
         }
+        const bool have_next = nxt >= 0;
         if (lm) {
             uint32_t leaf = 0;
             int k = 0, cnt = 0;
@@ -553,11 +616,10 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                             if (pm > -2) continue;  // a triangle lane
                             DHit hi{h.t, 0.f, 0.f, -1};
                             const bool ph = proxy_hit<ANY, COUNT, FAST, CHECK>(c, -2 - pm, r, tMin, hi, st, sp);
-                            if (st.overflow) return hit;
+                            if (st.overflow) return !ANY && h.prim >= 0;
                             if (ph) {
                                 if (ANY) return true;
                                 h.t = hi.t; h.a = hi.a; h.b = hi.b; h.prim = hi.prim; h.inst = -2 - pm;
-                                hit = true;
                             }
                         }
                     }
@@ -577,7 +639,6 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                     if (ANY) return true;   // (an any-hit walk: returning here measured faster than a flag)
                     h.t = t; h.a = a; h.b = b; h.prim = (int32_t)((leaf << 2) | (uint32_t)k);
                     if (INST) h.inst = -1;
-                    hit = true;
                 }
                 k++;
             }
@@ -606,7 +667,7 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
             else cur = stk_pop(c, sp);
         }
     }
-    return hit;
+    return !ANY && h.prim >= 0;
 }
 
 // One node visit of an any-hit traversal, resumable (traverse_impl's loop body
@@ -814,10 +875,11 @@ __device__ __forceinline__ bool anyhit_step_inst(const Trav& c, float tMin, floa
 // the adaptive kernel of plain scenes, and frame1_kernel's unless the host picks the nested
 // form (tuning walk_latch 0); any-hit walks and the chain engine keep the nested form
 // (round 6 A/B).
+// OROWS: scalar node fetches through the wave's octant rows (traverse_impl) -- frame1_kernel's walks.
 template <bool ANY, bool COUNT, bool FAST = false, bool INST = false, bool CHECK = true, bool LN = false,
-          bool XONE = false, bool OL = false>
+          bool XONE = false, bool OL = false, bool OROWS = false>
 __device__ __forceinline__ bool traverse(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st) {
-    const bool hit = (FAST && r.finite) ? traverse_impl<ANY, COUNT, true, INST, false, CHECK, LN, XONE, OL>(c, r, tMin, h, st)
+    const bool hit = (FAST && r.finite) ? traverse_impl<ANY, COUNT, true, INST, false, CHECK, LN, XONE, OL, OROWS>(c, r, tMin, h, st)
                                         : traverse_impl<ANY, COUNT, false, INST, false, CHECK, false, XONE, OL>(c, r, tMin, h, st);
     if (!ANY && hit) {
         h.prim = c.leaves[(uint32_t)h.prim >> 2].prim[h.prim & 3];
