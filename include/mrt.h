@@ -428,6 +428,12 @@ int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const floa
  * second exit on overflow; tuning "walk_exit" 0).  Both forms give the same bits. */
 int mrt_scene_walk_info(const mrt_scene* s, int32_t* lds_nodes, int32_t* walk_exits);
 
+/* The size limit of mrt_scene_upload: 1 when a device hierarchy of n_nodes nodes (128 B
+ * each) and n_leaves leaf packets (160 B each; the world's and every BLAS's together) has
+ * both arrays end within 4 GiB, else 0.  The walks address nodes and leaf triangles by
+ * 32-bit byte offsets; mrt_scene_upload refuses a larger scene with MRT_ERR_OVERFLOW. */
+int mrt_walk_arrays_fit(uint64_t n_nodes, uint64_t n_leaves);
+
 /* Counters of the last render on this scene (ray counts, visits, kernel time). */
 int mrt_scene_last_stats(const mrt_scene* s, mrt_stats* out);
 

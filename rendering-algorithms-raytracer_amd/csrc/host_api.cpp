@@ -641,6 +641,8 @@ int mrt_get_tuning(const char* key, int* value) {
     return MRT_OK;
 }
 
+int mrt_walk_arrays_fit(uint64_t n_nodes, uint64_t n_leaves) { return walk_arrays_fit(n_nodes, n_leaves) ? 1 : 0; }
+
 float mrt_rcp_nr(float x) { return rcp_nr(x, host_rcp_table()); }
 float mrt_rsqrt_nr(float x) { return rsqrt_nr(x, host_rsqrt_table()); }
 

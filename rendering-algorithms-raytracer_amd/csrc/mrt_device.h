@@ -80,6 +80,14 @@ struct Tuning {
 };
 extern Tuning g_tune;   // defined in host_api.cpp
 
+// The walks address a lane's node and leaf triangle as a 32-bit byte offset from the array's
+// base (node_at / tri_at, mrt_kernels.h), so a device node array (128 B per node) and leaf
+// array (160 B per packet) must each end within 4 GiB.  Upload refuses a scene past that
+// (MRT_ERR_OVERFLOW; mrt_walk_arrays_fit, host_api.cpp, is the same test on the C-ABI).
+inline bool walk_arrays_fit(uint64_t n_nodes, uint64_t n_leaves) {
+    return n_nodes <= (uint64_t(1) << 32) / 128 && n_leaves <= (uint64_t(1) << 32) / 160;
+}
+
 }  // namespace mrt
 
 #if defined(__HIPCC__)

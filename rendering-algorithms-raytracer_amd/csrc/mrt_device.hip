@@ -230,6 +230,7 @@ __global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DL
     const uint32_t gtid = blockIdx.x * kWG + tid;
     Trav T{nodes, fast_box != 0, false, leaves, s_tab, s_stack + tid, gstack + gtid, gstride};
     T.inst = insts;
+    T.ovf = ctr + CTR_OVERFLOW;
     T.aprims = alpha.aprims; T.apuv = alpha.apuv; T.auv = alpha.auv; T.amats = alpha.amats; T.atex = alpha.atex;
     T.pflags = alpha.pflags; T.verts = alpha.verts; T.verts2 = alpha.verts2;   // Ray time 0 (src/Ray.h:71)
     TravStats st;

@@ -85,12 +85,13 @@ struct Trav {
     const float4* verts2 = nullptr;
     bool near_first = false;   // any-hit walks descend into the nearest hit child first (order-free answer)
     const QNode* lnodes = nullptr;   // LN walks: nodes 0 .. kLdsNodes - 1 (the hierarchy's top levels) in LDS
+    unsigned long long* ovf = nullptr;   // the launch's overflow counter: one-exit walks report a full stack here themselves
 };
 
 struct TravStats {
     uint32_t nodes = 0, leaves = 0, uniform = 0;  // uniform: visits in wave-uniform node steps
     int max_sp = 0;
-    bool overflow = false;
+    bool overflow = false;   // set by the walks that return on a full stack (one-exit walks report through Trav::ovf)
 };
 
 __device__ __forceinline__ bool stk_push(const Trav& c, int& sp, int32_t v) {
@@ -103,6 +104,19 @@ __device__ __forceinline__ bool stk_push(const Trav& c, int& sp, int32_t v) {
 __device__ __forceinline__ int32_t stk_pop(const Trav& c, int& sp) {
     --sp;
     return sp < kLdsStack ? c.lds[sp * kWG] : c.gstk[(size_t)(sp - kLdsStack) * c.gstride];
+}
+
+// A lane's node / leaf triangle as the wave-uniform array base plus a 32-bit byte offset: one
+// or two 32-bit VALU and a load that takes the base from scalar registers, where the indexed
+// form builds a 64-bit address per lane (64-bit shifts and multiply-adds).  The offsets fit:
+// upload refuses a scene whose node or leaf array reaches 4 GiB (walk_arrays_fit, mrt_device.h).
+__device__ __forceinline__ const QNode* node_at(const QNode* __restrict__ nodes, int32_t i) {
+    return reinterpret_cast<const QNode*>(reinterpret_cast<const char*>(nodes) + (size_t)((uint32_t)i << 7));
+}
+__device__ __forceinline__ uint32_t tri_offset(uint32_t leaf, int k) { return leaf * 160u + (uint32_t)k * 36u; }
+__device__ __forceinline__ uint32_t tri_leaf(uint32_t toff, int k) { return (toff - (uint32_t)k * 36u) / 160u; }
+__device__ __forceinline__ const float* tri_at(const DLeaf* __restrict__ leaves, uint32_t toff) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(leaves) + (size_t)toff);
 }
 
 // v[i] for a lane-varying i as three selects (no divergent branch tree).
@@ -386,30 +400,31 @@ __device__ __forceinline__ DRay object_ray(const DevInstance& I, const DRay& r, 
     return make_ray(o, d, r.time);
 }
 
-// Triangle k of leaf packet `leaf` (intersect4's lane), for the active lanes of a
+// One triangle of a leaf packet (intersect4's lane), for the active lanes of a
 // traversal's flattened leaf loop.  When every active lane tests the same
 // triangle (coherent rays on one leaf: most primary and point-light shadow steps)
 // its 36 bytes come once through the scalar cache into SGPRs, not 64 times
 // through the vector path; tri_test then reads them as SGPR operands.  Distinct
 // markers end the two branches so the compiler cannot merge them (see
 // traverse_impl's node fetch).  The same test either way.
-__device__ __forceinline__ bool tri_test_lane(const Trav& c, uint32_t leaf, int k, const DRay& r, float tMin,
+// toff: the triangle's byte offset in the leaf array (tri_offset), which is also the key of
+// the uniformity test -- one offset, one triangle.
+__device__ __forceinline__ bool tri_test_lane(const Trav& c, uint32_t toff, const DRay& r, float tMin,
                                               float tBest, float& t, float& a, float& b) {
     int ok;
-    const uint32_t key = (leaf << 2) | (uint32_t)k;
-    // (scalar fetches switched off: bit 31, which no key has -- a leaf index has 28 bits -- makes
+    // (scalar fetches switched off: bit 0, which no offset has -- they are multiples of 4 -- makes
     // every lane differ, so the switch costs one scalar op here, not a test and a branch)
-    const uint32_t k0 = __builtin_amdgcn_readfirstlane(key) ^ ((c.scalar_nodes & 2) ? 0u : 0x80000000u);
-    if (__ballot(key != k0) == 0) {
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane(toff) ^ ((c.scalar_nodes & 2) ? 0u : 1u);
+    if (__ballot(toff != k0) == 0) {
         typedef const __attribute__((address_space(4))) float cfloat;
-        cfloat* q = (cfloat*)(const void*)(c.leaves[k0 >> 2].tri[k0 & 3]);
+        cfloat* q = (cfloat*)(const void*)tri_at(c.leaves, k0);
         float T[9];
 #pragma unroll
         for (int i = 0; i < 9; i++) T[i] = q[i];
         ok = tri_test(T, r, tMin, tBest, t, a, b, c.rcpT) ? 1 : 0;
         asm volatile("; mrt: scalar triangle" : "+v"(ok));
     } else {
-        ok = tri_test(c.leaves[leaf].tri[k], r, tMin, tBest, t, a, b, c.rcpT) ? 1 : 0;
+        ok = tri_test(tri_at(c.leaves, toff), r, tMin, tBest, t, a, b, c.rcpT) ? 1 : 0;
         asm volatile("; mrt: vector triangle" : "+v"(ok));
     }
     return ok != 0;
@@ -437,7 +452,9 @@ __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r
 
 // BVH::intersect, QBVH branch (src/BVH.cpp:1128-1178).  Returns hit; h.prim is
 // then the packed triangle slot (leaf << 2 | k), resolved by traverse().  On a
-// stack overflow st.overflow is set and the query is abandoned.
+// stack overflow the query is abandoned and the event reported: a two-exit walk
+// sets st.overflow and returns (its kernel's epilogue raises the launch's counter),
+// a one-exit walk (XONE) raises the counter itself (Trav::ovf) and carries no flag.
 // The caller enters with h.prim == -1: a closest-hit walk keeps no hit flag (a
 // loop-carried bool is a lane mask, re-formed at every merge point of the two
 // divergent loops on the scalar unit); every accept stores a packed slot >= 0
@@ -545,7 +562,7 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                                       : box_test_sel(bx, r, tMin, h.t, soct, present);
             asm volatile("; mrt: scalar node, any octant" : "+v"(m));
         } else {
-            const float4* q = reinterpret_cast<const float4*>(c.nodes + cur);
+            const float4* q = reinterpret_cast<const float4*>(node_at(c.nodes, cur));
             ch = reinterpret_cast<const int4*>(q)[6];
             kinds = node_kinds(q);
             m = FAST ? ((ANY && c.near_first) ? box_test_fast_t(q, r, tMin, h.t, tn) : box_test_sel(q, r, tMin, h.t, soct))
@@ -568,6 +585,8 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
             const int top = (FAST && ANY && c.near_first) ? nearest_slot(inner, tn) : 31 - __builtin_clz((unsigned)inner);
             const int rest = inner ^ (1 << top);
             nxt = sel4(ch, top);
+            // (the rare case decided once per wave, with the four LDS writes also run by the
+            // descending lanes that push nothing, measured 1.4% slower on C3: DESIGN §4)
             if (rest) {
                 if (sp + 4 <= kLdsStack) {
                     c.lds[sp * kWG] = ch.x; sp += rest & 1;
@@ -579,14 +598,20 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                         if ((rest >> i) & 1) pushed = pushed && stk_push(c, sp, sel4(ch, i));
-                    // overflow (flagged).  XONE: the walk ends at the loop's one exit (the pop
-                    // test below, with the stack emptied) instead of returning from here --
-                    // an extra exit of the divergent loop costs exec-mask bookkeeping in every
-                    // step (SALU -19% per step, C3 -7%, C4 -6%); the two-exit form stays as
-                    // tuning walk_exit 0 (round 6: the bunny scenes' tail effect)
+                    // overflow.  XONE: the walk ends at the loop's one exit (the pop test below,
+                    // with the stack emptied) instead of returning from here -- an extra exit of
+                    // the divergent loop costs exec-mask bookkeeping in every step (SALU -19%
+                    // per step, C3 -7%, C4 -6%); the two-exit form stays as tuning walk_exit 0
+                    // (round 6: the bunny scenes' tail effect).  XONE reports the
+                    // event from here (the launch's counter, Trav::ovf): a flag carried to the
+                    // kernel's end is a lane mask that every merge point of the push block
+                    // re-forms on the scalar unit, for an event no real scene has
                     if (!pushed) {
-                        st.overflow = true;
-                        if (!XONE) return !ANY && h.prim >= 0;
+                        if (!XONE) {
+                            st.overflow = true;
+                            return !ANY && h.prim >= 0;
+                        }
+                        atomicOr(c.ovf, 1ull);
                         sp = sp0;
                         nxt = -1;
                     }
@@ -596,7 +621,7 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
         }
         const bool have_next = nxt >= 0;
         if (lm) {
-            uint32_t leaf = 0;
+            uint32_t leaf = 0, toff = 0;   // toff: the current triangle's byte offset in the leaf array (tri_offset)
             int k = 0, cnt = 0;
             bool check = false;
             while (true) {
@@ -606,6 +631,7 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                     lm &= lm - 1;
                     const uint32_t v = ~(uint32_t)sel4(ch, s);
                     leaf = v >> 4;
+                    toff = tri_offset(leaf, 0);   // once per packet; the loop adds a triangle's 36 B
                     cnt = (int)(v & 3u) + 1;
                     k = 0;
                     check = CHECK && (INST || BL) && (v & 8u);
@@ -633,14 +659,17 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                              : tri_test(c.leaves[leaf].tri[k], r, tMin, h.t, t, a, b, c.rcpT);
                     ok = ok && !alpha_rejects(c, leaf, k, a, b, aoff);
                 } else {
-                    ok = tri_test_lane(c, leaf, k, r, tMin, h.t, t, a, b);
+                    ok = tri_test_lane(c, toff, r, tMin, h.t, t, a, b);
                 }
                 if (ok) {
                     if (ANY) return true;   // (an any-hit walk: returning here measured faster than a flag)
-                    h.t = t; h.a = a; h.b = b; h.prim = (int32_t)((leaf << 2) | (uint32_t)k);
+                    // (a plain walk carries the packet as toff only: its leaf index is formed here, per accept)
+                    const uint32_t lf = (INST || BL) ? leaf : tri_leaf(toff, k);
+                    h.t = t; h.a = a; h.b = b; h.prim = (int32_t)((lf << 2) | (uint32_t)k);
                     if (INST) h.inst = -1;
                 }
                 k++;
+                toff += 36u;
             }
         }
         if (OL) {

@@ -199,8 +199,10 @@ __device__ __forceinline__ uint32_t level_key(int level, int branch = 0) {
 // src/Ray.h:43-50): a per-lane LDS column in the REC kernels.
 static constexpr int kIorCap = 8;
 
-// the alpha-test tables of a traversal (special-leaf kernels only read them)
+// the alpha-test tables of a traversal (special-leaf kernels only read them) and the launch's
+// overflow counter (one-exit walks report a full stack there themselves, traverse_impl)
 __device__ __forceinline__ void trav_alpha(Trav& T, const RenderParams& P) {
+    T.ovf = P.ctr + CTR_OVERFLOW;
     T.aprims = P.prims;
     T.apuv = P.puv;
     T.auv = P.uvs;

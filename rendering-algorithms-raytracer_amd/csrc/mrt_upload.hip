@@ -285,6 +285,10 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
         for (int32_t& br : blas_root) br = perm[(size_t)br];
     }
     for (QNode& q : DN) q.pad[0] = slot_kinds(q.child);   // the walks read the slot kinds (node_kinds)
+    if (!walk_arrays_fit(DN.size(), DL.size())) {   // 32-bit byte offsets in the walks (node_at / tri_at)
+        set_error("scene too large: its node or leaf array passes 4 GiB");
+        return MRT_ERR_OVERFLOW;
+    }
     if ((rc = upload(d.nodes, DN.data(), DN.size() * sizeof(QNode), total))) return rc;
     std::vector<DevInstance> DI(s.instances.size());
     for (size_t i = 0; i < DI.size(); i++) {

@@ -29,6 +29,7 @@ EXPORTS = [
     "mrt_image_info", "mrt_image_load", "mrt_scene_add_texture_typed", "mrt_scene_set_material_maps",
     "mrt_scene_mesh_set_texcoords", "mrt_scene_mesh_texcoords", "mrt_scene_set_mesh_motion", "mrt_scene_walk_info",
     "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close", "mrt_get_tuning",
+    "mrt_walk_arrays_fit",
 ]
 
 
@@ -191,7 +192,9 @@ def load():
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
         L.mrt_get_tuning.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
-    L.mrt_debug_wave_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
+    if hasattr(L, "mrt_walk_arrays_fit"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_walk_arrays_fit.argtypes = [C.c_uint64, C.c_uint64]
+    L.mrt_debug_wave_log.argtypes =[C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
     L.mrt_device_wall_clock_khz.argtypes = [C.c_void_p]
     L.mrt_hdr_info.argtypes = [C.c_char_p, _ip, _ip]
     L.mrt_hdr_load.argtypes = [C.c_char_p, _fp, C.c_int32, C.c_int32]
