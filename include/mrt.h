@@ -421,6 +421,34 @@ int mrt_trace(mrt_scene* s, const float* o, const float* d, const float* tmin, c
 int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin,
                     const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream);
 
+/* ---- batched radiance query: Scene::sampleScene (src/Scene.cpp:219-243) for n caller
+ * rays.  o, d: n*3 floats (d is used as given, as Ray(o, d) does: not normalised); time:
+ * n floats or NULL (= 0, the Ray ctor default; the MBObject time of src/MBObject.cpp).
+ * rgb: n*3 floats (before Image::Map); hits: n primary hit records or NULL.  Ray i draws
+ * from the RNG stream of "pixel" i, eye-ray sample 0, of `seed` (0 = the default seed, as
+ * mrt_render_opts.seed).  row_width is a coherence hint only: > 0 says the batch is an
+ * image of rows of that many rays (waves then take 8x8 blocks of it); 0 = a list (a wave
+ * takes 64 consecutive rays).  Results never depend on it.  The scene's subdivision
+ * setting is ignored: one sampleScene per ray.  n is at most 2^28.  Runs on the scene's
+ * current device (device 0 before any upload), like mrt_trace.
+ * The synchronous form copies in and out; the async form takes device pointers, enqueues
+ * on `stream` and never synchronises.  Both fill mrt_scene_last_stats like a frame
+ * (primary_rays = n) and report MRT_ERR_OVERFLOW the same way (the async form from
+ * mrt_scene_last_stats).  On the rays of mrt_camera_rays(cam, W, H, seed) the result is
+ * the float frame and the hit records of mrt_render(cam, W x H, seed), bit for bit. */
+int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* time, size_t n,
+                    int32_t row_width, uint32_t seed, int32_t count_visits,
+                    float* rgb, mrt_hit* hits);
+int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time,
+                          size_t n, int32_t row_width, uint32_t seed, int32_t count_visits,
+                          float* d_rgb, mrt_hit* d_hits, void* stream);
+/* Camera::eyeRayAdaptive(x, y, .5, .5, .5, .5) (src/Camera.cpp:116-174) for every pixel of
+ * a width x height frame, on the host (no device is touched): the rays mrt_render traces
+ * at 1 spp with this seed, index y*width + x, lens and getTimeSample time included.
+ * o, d: width*height*3 floats; time: width*height floats. */
+int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32_t seed,
+                    float* o, float* d, float* time);
+
 /* The walk of the scene's last one-light frame on its current device: *lds_nodes = 1
  * when it ran the LDS top-node walk (tuning "lds_nodes"), 0 when not, -1 before any;
  * *walk_exits = the walk loop's form of the frame / primary kernels, 1 (one exit: a

@@ -102,7 +102,8 @@ struct UnitPix {
     int i, j;          // sub-cell of an adaptive pass n >= 2
     bool valid;
 };
-// unit ug of the pass (global index)
+// unit ug of the pass (global index); RAYS: ray mode (item_pixel: x = the ray, y = 0)
+template <bool RAYS = false>
 __device__ __forceinline__ UnitPix unit_pixel(const RenderParams& P, uint32_t ug) {
     UnitPix U;
     int item, lane;
@@ -120,13 +121,15 @@ __device__ __forceinline__ UnitPix unit_pixel(const RenderParams& P, uint32_t ug
         item = (int)(ug >> 6);
         lane = (int)(ug & 63u);
     }
-    U.valid = item_pixel(P, item, lane, U.x, U.y, U.slot);
-    U.f = item_frame(P, item);
+    U.valid = item_pixel<RAYS>(P, item, lane, U.x, U.y, U.slot);
+    U.f = item_frame<RAYS>(P, item);
     return U;
 }
 // the unit's eye ray: Camera::eyeRayAdaptive over the unit's cell (the centre
 // at pass 1 and without supersampling)
+template <bool RAYS = false>
 __device__ __forceinline__ EyeRay unit_eye(const RenderParams& P, const UnitPix& U, const uint16_t* rsqT) {
+    if constexpr (RAYS) return batch_ray(P, U.x);   // the caller's ray (never supersampled)
     const CamParams& cam = P.cam[U.f];
     const uint32_t seed = P.seed + (uint32_t)U.f;
     if (P.adapt_n <= 1) return camera_ray(cam, seed, U.x, U.y, rsqT);
@@ -139,7 +142,9 @@ __device__ __forceinline__ float4 unit_hit(const RenderParams& P, uint32_t u, co
 }
 // The camera ray's time of chunk path p (every ray below the camera ray carries
 // it): the getTimeSample draw of the unit's eye ray (shared by all its paths).
+template <bool RAYS = false>
 __device__ __forceinline__ float unit_time(const RenderParams& P, const UnitPix& U) {
+    if constexpr (RAYS) return P.rays_t ? P.rays_t[U.x] : 0.f;
     const CamParams& cam = P.cam[U.f];
     const float tr = rng((uint32_t)(U.y * cam.W + U.x), U.sample * 1024u, 2, P.seed + (uint32_t)U.f);
     return 1.f - ((tr * tr) * tr) * cam.shutter;
@@ -198,7 +203,7 @@ __device__ __forceinline__ void no_children(const RenderParams& P, uint32_t e) {
 // depend on the shadow answers); kResolve runs the same shading with the
 // answers and writes the path's value or marks it pending.  No traversal runs
 // in either, so the shading state never has to live across one.
-template <bool POINT_ONLY, bool INST, int REC, int MODE>
+template <bool POINT_ONLY, bool INST, int REC, int MODE, bool RAYS = false>
 __global__ void __launch_bounds__(kWG) chain0_kernel(RenderParams P) {
     __shared__ float s_ior[kIorCap * kWG];
     if (chunk_dead(P)) return;
@@ -212,7 +217,7 @@ __global__ void __launch_bounds__(kWG) chain0_kernel(RenderParams P) {
     for (uint32_t u0 = (uint32_t)blockIdx.x * kWG + (uint32_t)(tid & ~63); u0 < n; u0 += gridDim.x * (uint32_t)kWG) {
         const uint32_t u = u0 + (uint32_t)lane;
         if (u >= n) continue;
-        const UnitPix U = unit_pixel(P, P.unit_base + u);
+        const UnitPix U = unit_pixel<RAYS>(P, P.unit_base + u);
         DHit h{1e12f, 0.f, 0.f, -1};
         if (U.valid) {
             const float4 hv = unit_hit(P, u, U);
@@ -232,7 +237,7 @@ __global__ void __launch_bounds__(kWG) chain0_kernel(RenderParams P) {
         }
         const CamParams& cam = P.cam[U.f];
         const uint32_t seed = P.seed + (uint32_t)U.f;
-        const EyeRay er = unit_eye(P, U, rsqT);
+        const EyeRay er = unit_eye<RAYS>(P, U, rsqT);
         const DRay r = make_ray(er.o, er.d, er.time);
         Shader<POINT_ONLY, false, INST, MODE, REC> S{P, T, rcpT, rsqT, st, (uint32_t)(U.y * cam.W + U.x), 0u, seed, 0,
                                                      0u};
@@ -330,7 +335,7 @@ __global__ void __launch_bounds__(kWG) chain_compact_kernel(RenderParams P) {
 // anyhit_step_inst (2: alpha-mapped / motion-blurred lanes), one node per step for world
 // and BLAS nodes alike, the proxy walks deferred onto the stack (an any-hit answer does
 // not depend on the visit order), so lanes in and out of instances share every step.
-template <bool COUNT, bool FAST, bool INST, int MINW = 1, int STEP = 0>
+template <bool COUNT, bool FAST, bool INST, int MINW = 1, int STEP = 0, bool RAYS = false>
 __global__ void __launch_bounds__(kWG, MINW) chain_trace_kernel(RenderParams P) {
     __shared__ uint16_t s_tab[2048];
     __shared__ int32_t s_stack[kLdsStack * kWG];
@@ -366,7 +371,7 @@ __global__ void __launch_bounds__(kWG, MINW) chain_trace_kernel(RenderParams P) 
                 if (P.tr_perm) e = P.tr_perm[e];
                 const float4 o = P.ch_ray[2 * base + e], d = P.ch_ray[2 * base + cap + e];
                 float time = 0.f;
-                if (INST && P.has_mb) time = unit_time(P, unit_pixel(P, P.unit_base + __float_as_uint(o.w) / np));
+                if (INST && P.has_mb) time = unit_time<RAYS>(P, unit_pixel<RAYS>(P, P.unit_base + __float_as_uint(o.w) / np));
                 const DRay r = make_ray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), time);
                 DHit h{1e12f, 0.f, 0.f, -1};
                 const bool hit = traverse<false, COUNT, FAST, INST>(T, r, 0.001f, h, st);
@@ -457,7 +462,7 @@ __global__ void __launch_bounds__(kWG, MINW) chain_trace_kernel(RenderParams P) 
 // environment (or nothing: a GI ray without environment sampling; a split
 // child: nothing, flagged missed), a hit is shaded again with its shadow
 // answers and writes its value or marks itself pending.
-template <bool POINT_ONLY, bool INST, int REC, int MODE>
+template <bool POINT_ONLY, bool INST, int REC, int MODE, bool RAYS = false>
 __global__ void __launch_bounds__(kWG) chain_shade_kernel(RenderParams P) {
     __shared__ float s_ior[kIorCap * kWG];
     if (chunk_dead(P)) return;
@@ -498,7 +503,7 @@ __global__ void __launch_bounds__(kWG) chain_shade_kernel(RenderParams P) {
             }
             // the unit of path p (pixel, eye sample: the RNG keys; frame of a batched launch)
             const uint32_t u = p / np, path = p - u * np;
-            const UnitPix U = unit_pixel(P, P.unit_base + u);
+            const UnitPix U = unit_pixel<RAYS>(P, P.unit_base + u);
             const float4 i0 = P.ch_ior[2 * base + e], i1 = P.ch_ior[2 * base + cap + e];
             iorS[0] = 1.0f;
             iorS[1 * kWG] = i0.x; iorS[2 * kWG] = i0.y; iorS[3 * kWG] = i0.z; iorS[4 * kWG] = i0.w;
@@ -509,7 +514,7 @@ __global__ void __launch_bounds__(kWG) chain_shade_kernel(RenderParams P) {
                                                         shadow_base(P, k) + (size_t)e * (size_t)P.max_shadow, 0u};
             S.iorS = iorS;
             S.skey = U.sample * 1024u + path;
-            if (INST && P.has_mb) S.time = S.shadow_time = unit_time(P, U);
+            if (INST && P.has_mb) S.time = S.shadow_time = unit_time<RAYS>(P, U);
             typename Shader<POINT_ONLY, false, INST, MODE, REC>::IorCam icam;   // unused below the camera ray
             LevelOut lo;
             S.template level<false>(r, h, cs, icam, chain_rec(P, k, e), lo);
@@ -593,12 +598,13 @@ __global__ void __launch_bounds__(kWG) chain_fold_kernel(RenderParams P) {
 // as Scene::sampleScene does (src/Scene.cpp:224-233); a missed eye ray takes
 // the environment / background.  Frame / bucket mode: float RGB + Image::Map
 // 8-bit of the pixel; adaptive passes: the unit's colour (ucol).
+template <bool RAYS = false>
 __global__ void __launch_bounds__(kWG) chain_finish_kernel(RenderParams P) {
     if (chunk_dead(P)) return;
     const uint16_t* rsqT = P.tables + 2048;
     const uint32_t np = (uint32_t)P.num_paths, n = chunk_units(P);
     for (uint32_t u = blockIdx.x * kWG + threadIdx.x; u < n; u += gridDim.x * kWG) {
-        const UnitPix U = unit_pixel(P, P.unit_base + u);
+        const UnitPix U = unit_pixel<RAYS>(P, P.unit_base + u);
         if (!U.valid) continue;
         const float4 hv = unit_hit(P, u, U);
         v3 col;
@@ -610,7 +616,7 @@ __global__ void __launch_bounds__(kWG) chain_finish_kernel(RenderParams P) {
             }
             col = scale(result, 1.0f / (float)P.num_paths);
         } else {
-            col = P.env ? env_or_bg(P, unit_eye(P, U, rsqT).d) : mk(P.bg[0], P.bg[1], P.bg[2]);
+            col = P.env ? env_or_bg(P, unit_eye<RAYS>(P, U, rsqT).d) : mk(P.bg[0], P.bg[1], P.bg[2]);
         }
         if (P.ucol) {
             P.ucol[P.unit_base + u] = make_float4(col.x, col.y, col.z, 0.f);
@@ -708,7 +714,7 @@ __global__ void __launch_bounds__(64) chain_merge_kernel(RenderParams P) {
 // draws and adds as the engine -- tests/test_chain.py) from the units' eye-ray hits,
 // written as chain_finish writes them.  Nothing to do (one uniform load) otherwise.
 // COUNT: a count-mode frame, whose node / leaf visit statistics then include these units.
-template <bool POINT_ONLY, bool INST, int REC, bool COUNT>
+template <bool POINT_ONLY, bool INST, int REC, bool COUNT, bool RAYS = false>
 __global__ void __launch_bounds__(kWG) chain_fallback_kernel(RenderParams P) {
     __shared__ uint16_t s_tab[2048];
     __shared__ int32_t s_stack[kLdsStack * kWG];
@@ -725,11 +731,11 @@ __global__ void __launch_bounds__(kWG) chain_fallback_kernel(RenderParams P) {
     uint32_t shadow_total = 0, secondary_total = 0;
     const uint32_t n = chunk_units(P);
     for (uint32_t u = blockIdx.x * kWG + (uint32_t)tid; u < n; u += gridDim.x * kWG) {
-        const UnitPix U = unit_pixel(P, P.unit_base + u);
+        const UnitPix U = unit_pixel<RAYS>(P, P.unit_base + u);
         if (!U.valid) continue;
         const float4 hv = unit_hit(P, u, U);
         const DHit h{hv.x, hv.y, hv.z, __float_as_int(hv.w)};
-        const EyeRay er = unit_eye(P, U, rsqT);
+        const EyeRay er = unit_eye<RAYS>(P, U, rsqT);
         v3 col;
         if (h.prim >= 0) {
             const CamParams& cam = P.cam[U.f];
@@ -801,25 +807,41 @@ __global__ void __launch_bounds__(kWG) adapt_combine_kernel(RenderParams P) {
 }
 
 // kernel variants: point lights only x instanced scene x REC (1, 2) x MODE (gen, resolve)
-template <int MODE, int REC>
+// (R: the ray-mode instantiation)
+template <int MODE, int REC, bool R = false>
 static KernelFn chain0_fn(bool po, bool inst) {
-    return po ? (inst ? chain0_kernel<true, true, REC, MODE> : chain0_kernel<true, false, REC, MODE>)
-              : (inst ? chain0_kernel<false, true, REC, MODE> : chain0_kernel<false, false, REC, MODE>);
+    return po ? (inst ? chain0_kernel<true, true, REC, MODE, R> : chain0_kernel<true, false, REC, MODE, R>)
+              : (inst ? chain0_kernel<false, true, REC, MODE, R> : chain0_kernel<false, false, REC, MODE, R>);
 }
-template <int MODE, int REC>
+template <int MODE, int REC, bool R = false>
 static KernelFn chain_shade_fn(bool po, bool inst) {
-    return po ? (inst ? chain_shade_kernel<true, true, REC, MODE> : chain_shade_kernel<true, false, REC, MODE>)
-              : (inst ? chain_shade_kernel<false, true, REC, MODE> : chain_shade_kernel<false, false, REC, MODE>);
+    return po ? (inst ? chain_shade_kernel<true, true, REC, MODE, R> : chain_shade_kernel<true, false, REC, MODE, R>)
+              : (inst ? chain_shade_kernel<false, true, REC, MODE, R> : chain_shade_kernel<false, false, REC, MODE, R>);
 }
-KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec) {
-    if (rec == 2) return resolve ? chain0_fn<kResolve, 2>(po, inst) : chain0_fn<kGen, 2>(po, inst);
-    return resolve ? chain0_fn<kResolve, 1>(po, inst) : chain0_fn<kGen, 1>(po, inst);
+template <bool R>
+static KernelFn pick_chain0_r(bool resolve, bool po, bool inst, int rec) {
+    if (rec == 2) return resolve ? chain0_fn<kResolve, 2, R>(po, inst) : chain0_fn<kGen, 2, R>(po, inst);
+    return resolve ? chain0_fn<kResolve, 1, R>(po, inst) : chain0_fn<kGen, 1, R>(po, inst);
 }
-KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec) {
-    if (rec == 2) return resolve ? chain_shade_fn<kResolve, 2>(po, inst) : chain_shade_fn<kGen, 2>(po, inst);
-    return resolve ? chain_shade_fn<kResolve, 1>(po, inst) : chain_shade_fn<kGen, 1>(po, inst);
+KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec, bool rays) {
+    return rays ? pick_chain0_r<true>(resolve, po, inst, rec) : pick_chain0_r<false>(resolve, po, inst, rec);
 }
-KernelFn pick_chain_trace(bool c, bool f, bool inst, int step) {
+template <bool R>
+static KernelFn pick_chain_shade_r(bool resolve, bool po, bool inst, int rec) {
+    if (rec == 2) return resolve ? chain_shade_fn<kResolve, 2, R>(po, inst) : chain_shade_fn<kGen, 2, R>(po, inst);
+    return resolve ? chain_shade_fn<kResolve, 1, R>(po, inst) : chain_shade_fn<kGen, 1, R>(po, inst);
+}
+KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec, bool rays) {
+    return rays ? pick_chain_shade_r<true>(resolve, po, inst, rec) : pick_chain_shade_r<false>(resolve, po, inst, rec);
+}
+// the instanced variants read the unit's time (motion blur): a ray batch's comes from its time array
+template <int STEP>
+static KernelFn chain_trace_rays_fn(bool c, bool f) {
+    return c ? (f ? chain_trace_kernel<true, true, true, 1, STEP, true> : chain_trace_kernel<true, false, true, 1, STEP, true>)
+             : (f ? chain_trace_kernel<false, true, true, 1, STEP, true> : chain_trace_kernel<false, false, true, 1, STEP, true>);
+}
+KernelFn pick_chain_trace(bool c, bool f, bool inst, int step, bool rays) {
+    if (rays && inst) return step == 1 ? chain_trace_rays_fn<1>(c, f) : step == 2 ? chain_trace_rays_fn<2>(c, f) : chain_trace_rays_fn<0>(c, f);
     if (!c && !inst)   // occupancy target of the plain-scene trace (timed variants)
         return f ? chain_trace_kernel<false, true, false, 8> : chain_trace_kernel<false, false, false, 8>;
     if (inst && step == 1)
@@ -841,17 +863,18 @@ KernelFn pick_unit_eye(bool c, bool f, bool inst) {
 }
 KernelFn pick_chain_compact() { return chain_compact_kernel; }
 KernelFn pick_chain_merge() { return chain_merge_kernel; }
-template <bool C>
+template <bool C, bool R = false>
 static KernelFn chain_fallback_fn(bool po, bool inst, int rec) {
-    if (rec == 2) return po ? (inst ? chain_fallback_kernel<true, true, 2, C> : chain_fallback_kernel<true, false, 2, C>)
-                            : (inst ? chain_fallback_kernel<false, true, 2, C> : chain_fallback_kernel<false, false, 2, C>);
-    return po ? (inst ? chain_fallback_kernel<true, true, 1, C> : chain_fallback_kernel<true, false, 1, C>)
-              : (inst ? chain_fallback_kernel<false, true, 1, C> : chain_fallback_kernel<false, false, 1, C>);
+    if (rec == 2) return po ? (inst ? chain_fallback_kernel<true, true, 2, C, R> : chain_fallback_kernel<true, false, 2, C, R>)
+                            : (inst ? chain_fallback_kernel<false, true, 2, C, R> : chain_fallback_kernel<false, false, 2, C, R>);
+    return po ? (inst ? chain_fallback_kernel<true, true, 1, C, R> : chain_fallback_kernel<true, false, 1, C, R>)
+              : (inst ? chain_fallback_kernel<false, true, 1, C, R> : chain_fallback_kernel<false, false, 1, C, R>);
 }
-KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count) {
+KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count, bool rays) {
+    if (rays) return count ? chain_fallback_fn<true, true>(po, inst, rec) : chain_fallback_fn<false, true>(po, inst, rec);
     return count ? chain_fallback_fn<true>(po, inst, rec) : chain_fallback_fn<false>(po, inst, rec);
 }
-KernelFn pick_chain_finish() { return chain_finish_kernel; }
+KernelFn pick_chain_finish(bool rays) { return rays ? chain_finish_kernel<true> : chain_finish_kernel<false>; }
 KernelFn pick_chain_fold() { return chain_fold_kernel; }
 KernelFn pick_adapt_combine() { return adapt_combine_kernel; }
 

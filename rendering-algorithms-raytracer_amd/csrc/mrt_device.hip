@@ -247,6 +247,28 @@ __global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DL
     if (st.overflow) atomicOr(&ctr[CTR_OVERFLOW], 1ull);
 }
 
+// Device hit records (t, a, b, prim bits) -> mrt_hit (mrt_sample_rays_async): m_proxy from
+// the id, as to_hit() does on the host -- the last instance whose hit_base <= id.
+__global__ void __launch_bounds__(256) hit_records_kernel(const float4* rec, size_t n, const DevInstance* insts,
+                                                          int32_t n_insts, int32_t n_world, mrt_hit* out) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float4 v = rec[i];
+        mrt_hit h;
+        h.t = v.x; h.a = v.y; h.b = v.z;
+        h.prim = __float_as_int(v.w);
+        h.inst = -1;
+        if (h.prim >= n_world && n_insts > 0) {
+            int lo = 0, hi = n_insts - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (insts[mid].hit_base <= h.prim) lo = mid; else hi = mid - 1;
+            }
+            h.inst = lo;
+        }
+        out[i] = h;
+    }
+}
+
 // Bucket tiles -> frames.  Item id = frame * buckets_per_frame + bucket; frame f
 // of the output starts at f * W * H pixels.  Float tiles (nullable) go to
 // `frames`; 8-bit pixels come from tiles8 when given, else from the LUT.
@@ -618,12 +640,15 @@ static int chain_chunk(Scene& s, StreamCtx& c, RenderParams& Q, bool count, hipS
     DeviceState& d = *s.dev;
     const int L = Q.ch_levels;
     const bool inst = d.special;
-    const KernelFn g0 = pick_chain0(false, d.point_only, inst, d.recursive), r0 = pick_chain0(true, d.point_only, inst, d.recursive);
-    const KernelFn gk = pick_chain_shade(false, d.point_only, inst, d.recursive),
-                   rk = pick_chain_shade(true, d.point_only, inst, d.recursive);
+    const bool rays = Q.mode == 2;   // a ray batch: the kernels' ray-mode instantiations
+    const KernelFn g0 = pick_chain0(false, d.point_only, inst, d.recursive, rays),
+                   r0 = pick_chain0(true, d.point_only, inst, d.recursive, rays);
+    const KernelFn gk = pick_chain_shade(false, d.point_only, inst, d.recursive, rays),
+                   rk = pick_chain_shade(true, d.point_only, inst, d.recursive, rays);
     const KernelFn kc = pick_chain_compact(), kt = pick_chain_trace(count, Q.fast_box != 0, inst,
-                                                                           g_tune.chain_shadow_step ? (d.has_alpha || d.has_mb ? 2 : 1) : 0),
-                   kf = pick_chain_finish(), kd = pick_chain_fold();
+                                                                           g_tune.chain_shadow_step ? (d.has_alpha || d.has_mb ? 2 : 1) : 0,
+                                                                           rays),
+                   kf = pick_chain_finish(rays), kd = pick_chain_fold();
     auto go = [&](KernelFn f, int g) -> int {
         void* args[] = {&Q};
         HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(f), dim3(std::max(1, g)), dim3(kWG), args, 0, stream));
@@ -744,7 +769,7 @@ static int chain_chunk(Scene& s, StreamCtx& c, RenderParams& Q, bool count, hipS
     // fused (counted in the frame's statistics directly)
     void* margs[] = {&Q};
     HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(pick_chain_merge()), dim3(1), dim3(64), margs, 0, stream));
-    const KernelFn kfb = pick_chain_fallback(d.point_only, inst, d.recursive, count);
+    const KernelFn kfb = pick_chain_fallback(d.point_only, inst, d.recursive, count, rays);
     unsigned long long* cc = Q.ctr;
     Q.ctr = Q.ctr_out;
     rc = go(kfb, std::min(full(kfb), ug));
@@ -996,7 +1021,7 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
         }
         return done();
     }
-    c.fused = one && g_tune.fused;
+    c.fused = one && g_tune.fused && P.mode != 2;   // a ray batch: the two-launch path (frame1_kernel makes its own rays)
     if (c.fused) {   // one launch: camera rays, closest hits, shading, shadow rays
         if (!want_hits) P.hits = nullptr;
         // LDS top-node walk (tuning "lds_nodes"; both walks give the same bits)
@@ -1008,7 +1033,10 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
         return done();
     }
     const bool chk = d.has_alpha || d.has_mb;
-    if ((rc = launch(pick_primary(g_tune.primary_waves, count, fb, inst, chk, g_tune.walk_exit == 1)))) return rc;
+    const bool rays = P.mode == 2;   // a ray batch: the kernels' ray-mode instantiations
+    if ((rc = launch(rays ? pick_primary_rays(count, fb, inst, chk, g_tune.walk_exit == 1)
+                          : pick_primary(g_tune.primary_waves, count, fb, inst, chk, g_tune.walk_exit == 1))))
+        return rc;
     HIP_OK(hipEventRecord(c.evm, stream));
     P.queue = qbase + 8 * 32;
     const int max_sh = max_shadow_rays(s);
@@ -1022,7 +1050,10 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
         P.units_total = (uint32_t)P.n_tiles * 64u;
         if ((rc = launch_chain(s, c, P, count, stream, (uint64_t)P.n_tiles * 64, 64))) return rc;
     } else if (one || !wave) {
-        if ((rc = launch(one ? pick_shade1(count, fb, d.pow_spec) : pick_shade(count, d.point_only, fb, inst, d.recursive)))) return rc;
+        if ((rc = launch(one    ? pick_shade1(count, fb, d.pow_spec, rays)
+                         : rays ? pick_shade_rays(count, d.point_only, fb, inst, d.recursive)
+                                : pick_shade(count, d.point_only, fb, inst, d.recursive))))
+            return rc;
     } else {
         if ((rc = ensure_rays(c, slots, (size_t)max_sh))) return rc;
         P.ray_o = c.rays;
@@ -1039,7 +1070,8 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
             P.ray_e = c.ray_e;
             P.lrec = c.lrec;
         }
-        if ((rc = launch(shade_mode_fn<kGen>(count, d.point_only, inst)))) return rc;
+        if ((rc = launch(rays ? pick_shade_mode_rays(false, count, d.point_only, inst) : shade_mode_fn<kGen>(count, d.point_only, inst))))
+            return rc;
         // lane refill for dome-light (incoherent) rays: D1 -7%, C5 -13% shade pass; coherent
         // area-light rays keep the bands (C4: refill +9%)
         int sched = g_tune.shadow_sched >= 0 ? g_tune.shadow_sched : (dome ? 2 : 1), refill = kRefillMin;
@@ -1079,7 +1111,9 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
         P.sh_perm_n = nullptr;
         P.queue = qbase + 16 * 32;
         // dome-light resolve passes run faster at 4 waves (D1 -4%, C5 -1.2 ms), the rect-light one not (C4 +2%)
-        if ((rc = launch(shade_mode_fn<kResolve>(count, d.point_only, inst, dome)))) return rc;
+        if ((rc = launch(rays ? pick_shade_mode_rays(true, count, d.point_only, inst)
+                              : shade_mode_fn<kResolve>(count, d.point_only, inst, dome))))
+            return rc;
         P.ray_e = nullptr;
         P.lrec = nullptr;
         P.lcalls = 0;
@@ -1496,6 +1530,104 @@ int mrt_render(mrt_scene* s, const mrt_camera* cam, const mrt_render_opts* opts,
     S.last.primary_rays = px;
     mrt_stats tmp;
     if ((rc = mrt_scene_last_stats(s, &tmp))) return rc;
+    return MRT_OK;
+}
+
+// ---- Scene::sampleScene for caller rays (ray mode of the render dispatch, P.mode == 2)
+static constexpr size_t kMaxRayBatch = size_t(1) << 28;
+// the argument checks of both entries: before any device call
+static int sample_rays_check(const mrt_scene* s, const float* o, const float* d, size_t n, int32_t row_width,
+                             const float* rgb) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (n && (!o || !d || !rgb)) { set_error("null ray / output array"); return MRT_ERR_INVALID; }
+    if (row_width < 0) { set_error("row_width must be >= 0"); return MRT_ERR_INVALID; }
+    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    return MRT_OK;
+}
+
+int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
+                          int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, mrt_hit* d_hits,
+                          void* stream) {
+    int rc = sample_rays_check(s, d_o, d_d, n, row_width, d_rgb);
+    if (rc || n == 0) return rc;
+    Scene& S = s->impl;
+    const int dev = S.dev ? S.dev->device : 0;
+    if ((rc = ensure_device(S, dev))) return rc;
+    HIP_OK(hipSetDevice(dev));
+    RenderParams P{};
+    fill_params(S, P);
+    P.min_subdivs = P.max_subdivs = 1;   // one sampleScene per ray
+    P.seed = seed ? seed : 0x5EEDu;
+    P.mode = 2;
+    P.rays_o = d_o;
+    P.rays_d = d_d;
+    P.rays_t = d_time;
+    P.n_rays = (uint32_t)n;
+    // work items: 8x8 blocks of the ray image (a row at least as long as the batch is one row), or 64 rays in a row
+    const size_t w = std::min<size_t>((size_t)row_width, n);
+    P.ray_w = (int32_t)w;
+    P.tiles_x = w ? (int32_t)((w + 7) / 8) : 1;
+    P.n_tiles = w ? (int32_t)((size_t)P.tiles_x * (((n + w - 1) / w + 7) / 8)) : (int32_t)((n + 63) / 64);
+    P.out_rgb = d_rgb;
+    if ((rc = launch_render(S, P, n, count_visits != 0, (hipStream_t)stream, d_hits != nullptr))) return rc;
+    S.last.primary_rays = (uint64_t)n;
+    if (d_hits) {
+        const DeviceState& d = *S.dev;
+        const int g = (int)std::min<size_t>((n + 255) / 256, (size_t)d.cus * 8);
+        hipLaunchKernelGGL(hit_records_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, d.last->hitbuf, n, d.insts,
+                           (int32_t)d.n_insts, (int32_t)d.n_world, d_hits);
+        HIP_OK(hipGetLastError());
+    }
+    return MRT_OK;
+}
+
+int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* time, size_t n, int32_t row_width,
+                    uint32_t seed, int32_t count_visits, float* rgb, mrt_hit* hits) {
+    int rc = sample_rays_check(s, o, d, n, row_width, rgb);
+    if (rc || n == 0) return rc;
+    Scene& S = s->impl;
+    const int dev = S.dev ? S.dev->device : 0;
+    if ((rc = ensure_device(S, dev))) return rc;
+    HIP_OK(hipSetDevice(dev));
+    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *brgb = nullptr;
+    mrt_hit* bh = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void**)&bo, n * 12));
+        HIP_OK(hipMalloc((void**)&bd, n * 12));
+        HIP_OK(hipMalloc((void**)&brgb, n * 12));
+        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
+        if (hits) HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
+        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
+        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
+        int r = mrt_sample_rays_async(s, bo, bd, bt, n, row_width, seed, count_visits, brgb, bh, nullptr);
+        if (r) return r;
+        HIP_OK(hipMemcpy(rgb, brgb, n * 12, hipMemcpyDeviceToHost));
+        if (hits) HIP_OK(hipMemcpy(hits, bh, n * sizeof(mrt_hit), hipMemcpyDeviceToHost));
+        mrt_stats tmp;
+        return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
+    };
+    rc = run();
+    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(brgb); (void)hipFree(bh);
+    return rc;
+}
+
+int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32_t seed, float* o, float* d, float* time) {
+    if (!cam || !o || !d || !time) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    CamParams C;
+    int rc = host_camera(cam, width, height, C);   // (rejects a non-positive size)
+    if (rc) return rc;
+    const uint16_t* RS = host_rsqrt_table();
+    const uint32_t sd = seed ? seed : 0x5EEDu;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            const EyeRay er = camera_ray(C, sd, x, y, RS);   // the device's eye_ray(), compiled for the host
+            const size_t i = (size_t)y * (size_t)width + (size_t)x;
+            o[3 * i] = er.o.x; o[3 * i + 1] = er.o.y; o[3 * i + 2] = er.o.z;
+            d[3 * i] = er.d.x; d[3 * i + 1] = er.d.y; d[3 * i + 2] = er.d.z;
+            time[i] = er.time;
+        }
     return MRT_OK;
 }
 

@@ -95,7 +95,7 @@ __device__ __forceinline__ v3 shade1_hit(const RenderParams& P, const Trav& T, T
 
 // Kernel 2, specialised for one point light and num_paths == 1: shade1_hit of
 // every pixel's hit record (the two-launch path; frame1_kernel fuses both).
-template <bool COUNT, bool FAST, int MINW, bool POW>
+template <bool COUNT, bool FAST, int MINW, bool POW, bool RAYS = false>
 __global__ void __launch_bounds__(kWG, MINW) shade1_kernel(RenderParams P) {
     __shared__ uint16_t s_tab[2048];
     __shared__ int32_t s_stack[kLdsStack * kWG];
@@ -121,16 +121,16 @@ __global__ void __launch_bounds__(kWG, MINW) shade1_kernel(RenderParams P) {
         ntiles++;
         int x, y;
         size_t slot;
-        if (!item_pixel(P, item, lane, x, y, slot)) continue;
+        if (!item_pixel<RAYS>(P, item, lane, x, y, slot)) continue;
         const float4 hv = P.hits[slot];
         const int prim = __float_as_int(hv.w);
         v3 col = mk(P.bg[0], P.bg[1], P.bg[2]);
         if (prim >= 0) {
-            const int f = item_frame(P, item);
-            const EyeRay er = camera_ray(P.cam[f], P.seed + (uint32_t)f, x, y, rsqT);
+            const int f = item_frame<RAYS>(P, item);
+            const EyeRay er = source_ray<RAYS>(P, P.cam[f], P.seed + (uint32_t)f, x, y, rsqT);
             col = shade1_hit<COUNT, FAST, POW>(P, T, st, make_ray(er.o, er.d), hv.x, hv.y, hv.z, prim, rcpT, rsqT, shadow_total);
         }
-        item_pixel(P, item, lane, x, y, slot);
+        item_pixel<RAYS>(P, item, lane, x, y, slot);
         store_rgb(P, slot, col);
     }
     flush_stats<COUNT, false>(P, st, shadow_total, lane, t0, ntiles);
@@ -224,10 +224,10 @@ __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
     flush_stats<COUNT, false, false>(P, ss, shadow_total, lane_id(), t0, ntiles, 0, wave);
 }
 
-template <int W, bool POW>
+template <int W, bool POW, bool R = false>
 static KernelFn shade1_fn(bool c, bool f) {
-    return c ? (f ? shade1_kernel<true, true, W, POW> : shade1_kernel<true, false, W, POW>)
-             : (f ? shade1_kernel<false, true, W, POW> : shade1_kernel<false, false, W, POW>);
+    return c ? (f ? shade1_kernel<true, true, W, POW, R> : shade1_kernel<true, false, W, POW, R>)
+             : (f ? shade1_kernel<false, true, W, POW, R> : shade1_kernel<false, false, W, POW, R>);
 }
 template <int W, bool POW, int WALK>
 static KernelFn frame1_fn(bool c, bool f) {
@@ -256,5 +256,8 @@ KernelFn pick_frame1(int w, bool c, bool f, bool pow, int walk) {
     }
 }
 // (the two-launch path: fused = 0, or a caller that wants hit records) at 5 waves
-KernelFn pick_shade1(bool c, bool f, bool pow) { return pow ? shade1_fn<5, true>(c, f) : shade1_fn<5, false>(c, f); }
+KernelFn pick_shade1(bool c, bool f, bool pow, bool rays) {
+    if (rays) return pow ? shade1_fn<5, true, true>(c, f) : shade1_fn<5, false, true>(c, f);
+    return pow ? shade1_fn<5, true>(c, f) : shade1_fn<5, false>(c, f);
+}
 }  // namespace mrt

@@ -98,11 +98,26 @@ struct RenderParams {
     unsigned int* queue;         // 8 tile counters, 32 words apart (sched >= 2)
     // work: 8x8 tiles
     int32_t tiles_x, n_tiles;    // frame mode: tiles_x = ceil(W/8)
-    const int32_t* buckets;      // bucket mode: bucket ids (row-major bucket grid)
-    int32_t buckets_x;           // ceil(W/32)
-    int32_t buckets_per_frame;   // bucket mode: id = frame * buckets_per_frame + bucket
+    // (the ray mode's parameters share the words of ones only other modes read: a lane that
+    // spills the argument block copies all of it, so its size is part of every kernel's scratch)
+    union {
+        struct {
+            const int32_t* buckets;      // bucket mode: bucket ids (row-major bucket grid)
+            int32_t buckets_x;           // ceil(W/32)
+            int32_t buckets_per_frame;   // bucket mode: id = frame * buckets_per_frame + bucket
+        };
+        // ray mode (mrt_sample_rays; the RAYS instantiations of the kernels): the work units are
+        // caller rays.  Ray i is "pixel" (x = i, y = 0) of cam[0], whose W is 0 -- so the RNG's
+        // pixel key y * W + x is i -- with output slot i.  ray_w > 0: a work item is an 8x8 block
+        // of the ray image of rows of ray_w rays (tiles_x blocks per row); 0: 64 consecutive rays.
+        struct {
+            const float* rays_o;         // n_rays * 3: origins
+            int32_t ray_w;
+            uint32_t n_rays;
+        };
+    };
     int32_t n_cams;              // bucket mode: frames (cameras) in the batch
-    int32_t mode;                // 0 frame, 1 buckets
+    int32_t mode;                // 0 frame, 1 buckets, 2 rays (host side; the kernels: RAYS)
     int32_t frame_out;           // buckets: outputs are n_cams consecutive W*H frames, not tiles (store_rgb)
     float* out_rgb;              // frame: W*H*3; buckets: n_buckets*1024*3, or n_cams*W*H*3 with frame_out (nullable)
     uint8_t* out_rgb8;           // same slots as out_rgb (nullable)
@@ -139,8 +154,16 @@ struct RenderParams {
     int32_t adapt_n;             // adaptive supersampling pass (level) n; 0: no adaptive supersampling
     float4* uhits;               // adaptive: closest hit per unit of the chunk (null: hits[pixel slot])
     float4* ucol;                // adaptive: colour per unit of the pass
-    float4* adapt_res;           // adaptive: running mean per pixel slot
-    uint32_t* next_units;        // adaptive combine: the pixels that refine further
+    union {
+        struct {
+            float4* adapt_res;           // adaptive: running mean per pixel slot
+            uint32_t* next_units;        // adaptive combine: the pixels that refine further
+        };
+        struct {                         // ray mode (never supersampled)
+            const float* rays_d;         // n_rays * 3: directions, used as given
+            const float* rays_t;         // n_rays times (nullable: 0)
+        };
+    };
     uint32_t* next_cnt;
     const uint32_t* sh_count;    // shadow_kernel: pixel / entry count on the device (nullable)
     // ray binning (mrt_bin.h): the trace kernels take their rays in this order
@@ -1108,14 +1131,32 @@ struct TileSched {
 };
 
 // work item (8x8 tile, wave-uniform) -> frame of the item (frame mode: 0)
+template <bool RAYS = false>
 __device__ __forceinline__ int item_frame(const RenderParams& P, int item) {
+    if constexpr (RAYS) return 0;
     // clamped: an out-of-range id renders with the last camera instead of reading
     // past the kernel argument block
     return P.mode == 0 ? 0 : (int)min((uint32_t)P.buckets[item >> 4] / (uint32_t)P.buckets_per_frame, (uint32_t)(P.n_cams - 1));
 }
 
-// work item + lane -> pixel (x, y) and output slot
+// work item + lane -> pixel (x, y) and output slot.  RAYS: -> ray index i as x (y = 0), slot i;
+// the ragged last row and the last partial wave are inactive
+template <bool RAYS = false>
 __device__ __forceinline__ bool item_pixel(const RenderParams& P, int item, int lane, int& x, int& y, size_t& slot) {
+    if constexpr (RAYS) {
+        size_t i;
+        if (P.ray_w > 0) {
+            const int cx = (item % P.tiles_x) * 8 + (lane & 7);
+            i = (size_t)((item / P.tiles_x) * 8 + (lane >> 3)) * (size_t)P.ray_w + (size_t)cx;
+            if (cx >= P.ray_w) i = P.n_rays;
+        } else {
+            i = (size_t)item * 64 + (size_t)lane;
+        }
+        x = (int)i;
+        y = 0;
+        slot = i;
+        return i < (size_t)P.n_rays;
+    }
     if (P.mode == 0) {
         int tx = item % P.tiles_x, ty = item / P.tiles_x;
         x = tx * 8 + (lane & 7);
@@ -1231,8 +1272,8 @@ struct EyeRay {
     v3 o, d;
     float time;
 };
-__device__ __forceinline__ EyeRay eye_ray(const CamParams& cam, uint32_t seed, int x, int y, uint32_t skey, float x0,
-                                          float x1, float y0, float y1, const uint16_t* rsqT) {
+MRT_HD EyeRay eye_ray(const CamParams& cam, uint32_t seed, int x, int y, uint32_t skey, float x0,
+                      float x1, float y0, float y1, const uint16_t* rsqT) {
     const uint32_t pixel = (uint32_t)(y * cam.W + x);
     const float ur = rng(pixel, skey, 0, seed), vr = rng(pixel, skey, 1, seed);
     const float xo = (x1 - x0) * ur + x0, yo = (y1 - y0) * vr + y0;
@@ -1256,15 +1297,30 @@ __device__ __forceinline__ EyeRay eye_ray(const CamParams& cam, uint32_t seed, i
     return EyeRay{o, normalized(sub(focal, o), rsqT), time};
 }
 // the 1-spp camera ray (eyeRayAdaptive(x, y, .5, .5, .5, .5), sample 0)
-__device__ __forceinline__ EyeRay camera_ray(const CamParams& cam, uint32_t seed, int x, int y, const uint16_t* rsqT) {
+MRT_HD EyeRay camera_ray(const CamParams& cam, uint32_t seed, int x, int y, const uint16_t* rsqT) {
     return eye_ray(cam, seed, x, y, 0u, 0.5f, 0.5f, 0.5f, 0.5f, rsqT);
+}
+// caller ray i of a ray batch: Ray(o, d) as given, time 0 without a time array
+__device__ __forceinline__ EyeRay batch_ray(const RenderParams& P, int i) {
+    const float* o = P.rays_o + 3 * (size_t)i;
+    const float* d = P.rays_d + 3 * (size_t)i;
+    return EyeRay{mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]), P.rays_t ? P.rays_t[i] : 0.f};
+}
+// the 1-spp ray of the unit item_pixel() put at (x, y): the eye ray of camera `cam` / `seed`,
+// or (RAYS) the caller's ray x
+template <bool RAYS>
+__device__ __forceinline__ EyeRay source_ray(const RenderParams& P, const CamParams& cam, uint32_t seed, int x, int y,
+                                             const uint16_t* rsqT) {
+    if constexpr (RAYS) return batch_ray(P, x);
+    else return camera_ray(cam, seed, x, y, rsqT);
 }
 
 // Kernel 1: Camera::eyeRayAdaptive + closest-hit BVH::intersect per pixel.
 // Writes the HitInfo record (t, a, b, prim) to P.hits[slot].
 // CHECK: the special-leaf scene has alpha-mapped or motion-blurred lanes (false: instances only)
 // XONE: the walk loop's exit form (traverse_impl; same bits), picked per scene by the host
-template <bool COUNT, int MINW, bool FAST, bool INST = false, bool CHECK = true, bool XONE = false>
+// RAYS: the work units are the caller's rays (ray mode), not a camera's pixels
+template <bool COUNT, int MINW, bool FAST, bool INST = false, bool CHECK = true, bool XONE = false, bool RAYS = false>
 __global__ void __launch_bounds__(kWG, MINW) primary_kernel(RenderParams P) {
     __shared__ uint16_t s_tab[2048];
     __shared__ int32_t s_stack[kLdsStack * kWG];
@@ -1294,15 +1350,15 @@ __global__ void __launch_bounds__(kWG, MINW) primary_kernel(RenderParams P) {
         int x, y;
         size_t slot;
         const uint32_t n0 = st.nodes;
-        if (item_pixel(PA, item, lane_id(), x, y, slot)) {
-            const int f = item_frame(PA, item);
+        if (item_pixel<RAYS>(PA, item, lane_id(), x, y, slot)) {
+            const int f = item_frame<RAYS>(PA, item);
             const CamParams& cam = PA.cam[f];
-            const EyeRay er = camera_ray(cam, PA.seed + (uint32_t)f, x, y, rsqT);
+            const EyeRay er = source_ray<RAYS>(PA, cam, PA.seed + (uint32_t)f, x, y, rsqT);
             DRay r = make_ray(er.o, er.d, er.time);
             DHit h{1e12f, 0.f, 0.f, -1};
             if (!traverse<false, COUNT, FAST, INST, CHECK, false, XONE, XONE && !INST>(T, r, 0.001f, h, st)) h.prim = -1;
             const RenderParams& PC = reload_params();
-            item_pixel(PC, item, lane_id(), x, y, slot);  // recompute: keeps it out of the traversal's live set
+            item_pixel<RAYS>(PC, item, lane_id(), x, y, slot);  // recompute: keeps it out of the traversal's live set
             PC.hits[slot] = make_float4(h.t, h.a, h.b, __int_as_float(h.prim));
             nhits += h.prim >= 0 ? 1u : 0u;  // wave-reduced in flush_stats
         }
@@ -1317,7 +1373,8 @@ __global__ void __launch_bounds__(kWG, MINW) primary_kernel(RenderParams P) {
 }
 
 // Kernel 2: Scene::sampleScene shading of the primary hit with shadow rays.
-template <bool COUNT, bool POINT_ONLY, bool FAST, bool INST = false, int MODE = kFused, int REC = 0, int MINW = 1>
+template <bool COUNT, bool POINT_ONLY, bool FAST, bool INST = false, int MODE = kFused, int REC = 0, int MINW = 1,
+          bool RAYS = false>
 __global__ void __launch_bounds__(kWG, MINW) shade_kernel(RenderParams P) {
     __shared__ uint16_t s_tab[2048];
     __shared__ int32_t s_stack[kLdsStack * kWG];
@@ -1344,18 +1401,18 @@ __global__ void __launch_bounds__(kWG, MINW) shade_kernel(RenderParams P) {
         ntiles++;
         int x, y;
         size_t slot;
-        if (!item_pixel(P, item, lane, x, y, slot)) {
-            if (MODE == kGen && P.mode != 0) P.nrays[slot] = 0;  // bucket slot outside the frame
+        if (!item_pixel<RAYS>(P, item, lane, x, y, slot)) {
+            if (!RAYS && MODE == kGen && P.mode != 0) P.nrays[slot] = 0;  // bucket slot outside the frame
             continue;
         }
         float4 hv = P.hits[slot];
         DHit h{hv.x, hv.y, hv.z, __float_as_int(hv.w)};
         v3 col;
         if (h.prim >= 0) {
-            const int f = item_frame(P, item);
+            const int f = item_frame<RAYS>(P, item);
             const CamParams& cam = P.cam[f];
             const uint32_t seed = P.seed + (uint32_t)f;
-            const EyeRay er = camera_ray(cam, seed, x, y, rsqT);
+            const EyeRay er = source_ray<RAYS>(P, cam, seed, x, y, rsqT);
             DRay r = make_ray(er.o, er.d, er.time);
             Shader<POINT_ONLY, FAST, INST, MODE, REC> S{P, T, rcpT, rsqT, st, (uint32_t)(y * cam.W + x), 0u, seed,
                                                    slot * (size_t)P.max_shadow, 0u};
@@ -1370,8 +1427,8 @@ __global__ void __launch_bounds__(kWG, MINW) shade_kernel(RenderParams P) {
             P.nrays[slot] = 0;
             continue;
         } else if (P.env) {  // environment map lookup of the missed ray (src/Scene.cpp:236-239)
-            const int f = item_frame(P, item);
-            const v3 d = camera_ray(P.cam[f], P.seed + (uint32_t)f, x, y, rsqT).d;
+            const int f = item_frame<RAYS>(P, item);
+            const v3 d = source_ray<RAYS>(P, P.cam[f], P.seed + (uint32_t)f, x, y, rsqT).d;
             col = scale(tex_lookup_dir(P.env, P.env_w, P.env_h, d.x, d.y, d.z), P.env_exposure);
         } else {
             col = mk(P.bg[0], P.bg[1], P.bg[2]);
@@ -1564,6 +1621,7 @@ __global__ void __launch_bounds__(kWG, MINW) adaptive_kernel(RenderParams P) {
 
 using KernelFn = void (*)(RenderParams);
 
+// K: a kernel family over <COUNT, POINT_ONLY, FAST, INST, REC> (ShadeK, AdaptK, ...)
 template <template <bool, bool, bool, bool, int> class K, int REC>
 static KernelFn pick4(bool c, bool po, bool f, bool inst) {
     if (inst) return c ? (f ? K<true, false, true, true, REC>::fn : K<true, false, false, true, REC>::fn)
@@ -1575,23 +1633,30 @@ static KernelFn pick4(bool c, bool po, bool f, bool inst) {
 }
 template <bool C, bool PO, bool F, bool I, int REC>
 struct ShadeK { static constexpr KernelFn fn = shade_kernel<C, PO, F, I, kFused, REC>; };
+template <bool C, bool PO, bool F, bool I, int REC>
+struct ShadeRaysK { static constexpr KernelFn fn = shade_kernel<C, PO, F, I, kFused, REC, 1, true>; };
 
 // defined in mrt_frame.hip: the one-point-light frame / shade kernels at an
 // occupancy target w; pow: a Blinn material with specExp != 1
 KernelFn pick_frame1(int w, bool c, bool f, bool pow, int walk);
-KernelFn pick_shade1(bool c, bool f, bool pow);
+KernelFn pick_shade1(bool c, bool f, bool pow, bool rays = false);
 // defined in mrt_rec.hip: the fused chain kernels (rec 1: reflection / refraction,
 // 2: + path tracing) and the adaptive supersampling kernels (any rec)
 KernelFn pick_shade_rec(bool c, bool po, bool f, bool inst, int rec);
 KernelFn pick_adaptive(bool c, bool po, bool f, bool inst, int rec);
 // defined in mrt_chain.hip: the wavefront chain engine
-KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec);
-KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec);
-KernelFn pick_chain_trace(bool c, bool f, bool inst, int step);
+// (rays: the ray-mode instantiations -- the kernels that look at a unit's pixel or eye ray)
+KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec, bool rays = false);
+KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec, bool rays = false);
+KernelFn pick_chain_trace(bool c, bool f, bool inst, int step, bool rays = false);
 KernelFn pick_chain_compact();
 KernelFn pick_chain_merge();
-KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count);
-KernelFn pick_chain_finish();
+KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count, bool rays = false);
+KernelFn pick_chain_finish(bool rays = false);
+// defined in mrt_rays.hip: the ray-mode instantiations of the primary / shading kernels
+KernelFn pick_primary_rays(bool c, bool f, bool inst, bool check, bool xone);
+KernelFn pick_shade_rays(bool c, bool po, bool f, bool inst, int rec);
+KernelFn pick_shade_mode_rays(bool resolve, bool c, bool po, bool inst);
 KernelFn pick_chain_fold();
 KernelFn pick_unit_eye(bool c, bool f, bool inst);
 KernelFn pick_adapt_combine();

@@ -359,6 +359,20 @@ class Camera:
         return _lib.mrt_camera(f3(self.eye), f3(self.lookAt), f3(self.up), self.fov, self.aperture, self.focusPlane,
                                self.shutterSpeed)
 
+    def rays(self, width, height, seed=0):
+        """Camera::eyeRayAdaptive(x, y, .5, .5, .5, .5) of every pixel (mrt_camera_rays, on the
+        host): (o, d, time) of shapes (H, W, 3), (H, W, 3), (H, W) -- the rays raytraceImage
+        traces for a width x height frame with this seed (Scene.sampleRays shades them)."""
+        W, H = int(width), int(height)
+        if W <= 0 or H <= 0:
+            raise MRTError("Camera.rays: the frame size must be positive")
+        o, d = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        t = np.zeros((H, W), np.float32)
+        c = self._c()
+        check(lib().mrt_camera_rays(C.byref(c), W, H, int(seed), o.ctypes.data, d.ctypes.data, t.ctypes.data),
+              "camera_rays")
+        return o, d, t
+
 
 class Image:
     """Image (src/Image.h): 8-bit RGB, row 0 = bottom, plus the float RGB frame
@@ -741,6 +755,51 @@ class Scene:
         check(lib().mrt_trace(self.handle, o.ctypes.data_as(fp), d.ctypes.data_as(fp), tmin.ctypes.data_as(fp),
                               tmax.ctypes.data_as(fp), n, int(any_hit), out.ctypes.data), "trace")
         return out
+
+    # -- Scene::sampleScene for caller rays (src/Scene.cpp:219-243)
+    def sampleRays(self, o, d, time=None, seed=0, want_hits=False, count_visits=False, row_width=None):
+        """Radiance along caller rays (mrt_sample_rays): closest hit, m_numPaths shade() calls
+        averaged, environment / background on a miss.  o, d: (n, 3) or (H, W, 3); time: (n,) /
+        (H, W) or None (0).  numpy arrays go through the synchronous entry; torch device tensors
+        through mrt_sample_rays_async on the current stream, with no host copy (float32,
+        contiguous, on the scene's device).  row_width (coherence hint, never changes a result):
+        default W for an (H, W, 3) input, else 0.  Returns rgb in the input's shape -- and the
+        primary hit records (HIT_DTYPE; an (n, 5) int32 device tensor of t, a, b bits, prim,
+        inst for tensors) when want_hits.  Ray i draws from RNG stream i of `seed`."""
+        L = lib()
+        shape = tuple(o.shape)
+        if len(shape) not in (2, 3) or shape[-1] != 3 or tuple(d.shape) != shape:
+            raise MRTError("sampleRays: o and d must both be (n, 3) or (H, W, 3)")
+        n = int(np.prod(shape[:-1]))
+        if time is not None and int(np.prod(tuple(time.shape))) != n:
+            raise MRTError("sampleRays: time must hold one value per ray")
+        if row_width is None:
+            row_width = shape[1] if len(shape) == 3 else 0
+        check(L.mrt_scene_upload(self.handle, self.device), "upload")
+        if hasattr(o, "data_ptr"):   # torch device tensors: enqueue on the current stream
+            import torch
+            ts = [o, d] + ([time] if time is not None else [])
+            for x in ts:
+                if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.device.index == self.device):
+                    raise MRTError("sampleRays: tensors must be contiguous float32 on the scene's device")
+            rgb = torch.empty(shape, dtype=torch.float32, device=o.device)
+            hits = torch.empty((n, 5), dtype=torch.int32, device=o.device) if want_hits else None
+            stream = torch.cuda.current_stream(o.device).cuda_stream
+            check(L.mrt_sample_rays_async(self.handle, o.data_ptr(), d.data_ptr(),
+                                          time.data_ptr() if time is not None else None, n, int(row_width), int(seed),
+                                          int(count_visits), rgb.data_ptr(), hits.data_ptr() if want_hits else None,
+                                          stream), "sampleRays")
+            return (rgb, hits) if want_hits else rgb
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        t = np.ascontiguousarray(time, np.float32) if time is not None else None
+        rgb = np.zeros(shape, np.float32)
+        hits = np.zeros(shape[:-1], HIT_DTYPE) if want_hits else None
+        check(L.mrt_sample_rays(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None, n,
+                                int(row_width), int(seed), int(count_visits), rgb.ctypes.data,
+                                hits.ctypes.data if want_hits else None), "sampleRays")
+        self.last_stats = self.stats()
+        return (rgb, hits) if want_hits else rgb
 
     def primObject(self, prim: int):
         """HitInfo::obj / m_proxy of a hit id: (mesh id, triangle index, instance or -1)."""

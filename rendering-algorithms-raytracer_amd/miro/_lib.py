@@ -29,7 +29,7 @@ EXPORTS = [
     "mrt_image_info", "mrt_image_load", "mrt_scene_add_texture_typed", "mrt_scene_set_material_maps",
     "mrt_scene_mesh_set_texcoords", "mrt_scene_mesh_texcoords", "mrt_scene_set_mesh_motion", "mrt_scene_walk_info",
     "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close", "mrt_get_tuning",
-    "mrt_walk_arrays_fit",
+    "mrt_walk_arrays_fit", "mrt_sample_rays", "mrt_sample_rays_async", "mrt_camera_rays",
 ]
 
 
@@ -188,6 +188,13 @@ def load():
     L.mrt_trace.argtypes = [C.c_void_p, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_void_p]
     L.mrt_trace_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mrt_sample_rays"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_sample_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                      C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mrt_sample_rays_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                            C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mrt_camera_rays.argtypes = [C.POINTER(mrt_camera), C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
