@@ -374,7 +374,7 @@ __global__ void __launch_bounds__(kWG, MINW) chain_trace_kernel(RenderParams P) 
                 if (INST && P.has_mb) time = unit_time<RAYS>(P, unit_pixel<RAYS>(P, P.unit_base + __float_as_uint(o.w) / np));
                 const DRay r = make_ray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), time);
                 DHit h{1e12f, 0.f, 0.f, -1};
-                const bool hit = traverse<false, COUNT, FAST, INST>(T, r, 0.001f, h, st);
+                const bool hit = traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST)>(T, r, 0.001f, h, st);
                 P.ch_hit[base + e] = make_float4(h.t, h.a, h.b, __int_as_float(hit ? h.prim : -1));
             }
         } else {         // shadow ray j of level k - 1's entry (or path) s, any hit
@@ -402,7 +402,8 @@ __global__ void __launch_bounds__(kWG, MINW) chain_trace_kernel(RenderParams P) 
                     P.occl[sb + i] = hit ? 1 : 0;
                 } else {
                     DHit h{o.w, 0.f, 0.f, -1};
-                    P.occl[sb + i] = traverse<true, COUNT, FAST, INST>(T, r, 0.001f, h, st) ? 1 : 0;
+                    constexpr uint32_t ANYHIT = W_ANY | walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST);
+                    P.occl[sb + i] = traverse<ANYHIT>(T, r, 0.001f, h, st) ? 1 : 0;
                 }
             }
         }
@@ -652,7 +653,8 @@ __global__ void __launch_bounds__(kWG, MINW) unit_eye_kernel(RenderParams P) {
         bool hit = false;
         if (U.valid) {
             const EyeRay er = unit_eye(P, U, rsqT);
-            hit = traverse<false, COUNT, FAST, INST>(T, make_ray(er.o, er.d, er.time), 0.001f, h, st);
+            constexpr uint32_t CLOSEST = walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST);
+            hit = traverse<CLOSEST>(T, make_ray(er.o, er.d, er.time), 0.001f, h, st);
             rays++;
             hits += hit ? 1u : 0u;
         }
@@ -807,72 +809,40 @@ __global__ void __launch_bounds__(kWG) adapt_combine_kernel(RenderParams P) {
 }
 
 // kernel variants: point lights only x instanced scene x REC (1, 2) x MODE (gen, resolve)
-// (R: the ray-mode instantiation)
-template <int MODE, int REC, bool R = false>
-static KernelFn chain0_fn(bool po, bool inst) {
-    return po ? (inst ? chain0_kernel<true, true, REC, MODE, R> : chain0_kernel<true, false, REC, MODE, R>)
-              : (inst ? chain0_kernel<false, true, REC, MODE, R> : chain0_kernel<false, false, REC, MODE, R>);
-}
-template <int MODE, int REC, bool R = false>
-static KernelFn chain_shade_fn(bool po, bool inst) {
-    return po ? (inst ? chain_shade_kernel<true, true, REC, MODE, R> : chain_shade_kernel<true, false, REC, MODE, R>)
-              : (inst ? chain_shade_kernel<false, true, REC, MODE, R> : chain_shade_kernel<false, false, REC, MODE, R>);
-}
-template <bool R>
-static KernelFn pick_chain0_r(bool resolve, bool po, bool inst, int rec) {
-    if (rec == 2) return resolve ? chain0_fn<kResolve, 2, R>(po, inst) : chain0_fn<kGen, 2, R>(po, inst);
-    return resolve ? chain0_fn<kResolve, 1, R>(po, inst) : chain0_fn<kGen, 1, R>(po, inst);
-}
+// x the ray-mode instantiation
 KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec, bool rays) {
-    return rays ? pick_chain0_r<true>(resolve, po, inst, rec) : pick_chain0_r<false>(resolve, po, inst, rec);
-}
-template <bool R>
-static KernelFn pick_chain_shade_r(bool resolve, bool po, bool inst, int rec) {
-    if (rec == 2) return resolve ? chain_shade_fn<kResolve, 2, R>(po, inst) : chain_shade_fn<kGen, 2, R>(po, inst);
-    return resolve ? chain_shade_fn<kResolve, 1, R>(po, inst) : chain_shade_fn<kGen, 1, R>(po, inst);
+    return with_bools([](auto R, auto REC2, auto RES, auto PO, auto I) -> KernelFn {
+        return chain0_kernel<PO(), I(), REC2() ? 2 : 1, RES() ? kResolve : kGen, R()>;
+    }, rays, rec == 2, resolve, po, inst);
 }
 KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec, bool rays) {
-    return rays ? pick_chain_shade_r<true>(resolve, po, inst, rec) : pick_chain_shade_r<false>(resolve, po, inst, rec);
-}
-// the instanced variants read the unit's time (motion blur): a ray batch's comes from its time array
-template <int STEP>
-static KernelFn chain_trace_rays_fn(bool c, bool f) {
-    return c ? (f ? chain_trace_kernel<true, true, true, 1, STEP, true> : chain_trace_kernel<true, false, true, 1, STEP, true>)
-             : (f ? chain_trace_kernel<false, true, true, 1, STEP, true> : chain_trace_kernel<false, false, true, 1, STEP, true>);
+    return with_bools([](auto R, auto REC2, auto RES, auto PO, auto I) -> KernelFn {
+        return chain_shade_kernel<PO(), I(), REC2() ? 2 : 1, RES() ? kResolve : kGen, R()>;
+    }, rays, rec == 2, resolve, po, inst);
 }
 KernelFn pick_chain_trace(bool c, bool f, bool inst, int step, bool rays) {
-    if (rays && inst) return step == 1 ? chain_trace_rays_fn<1>(c, f) : step == 2 ? chain_trace_rays_fn<2>(c, f) : chain_trace_rays_fn<0>(c, f);
+    // the instanced variants read the unit's time (motion blur): a ray batch's comes from its time array
+    if (rays && inst) return with_ints<1, 2, 0>(step, [&](auto S) {
+        return with_bools([](auto C, auto F) -> KernelFn { return chain_trace_kernel<C(), F(), true, 1, decltype(S)::value, true>; }, c, f);
+    });
     if (!c && !inst)   // occupancy target of the plain-scene trace (timed variants)
-        return f ? chain_trace_kernel<false, true, false, 8> : chain_trace_kernel<false, false, false, 8>;
-    if (inst && step == 1)
-        return c ? (f ? chain_trace_kernel<true, true, true, 1, 1> : chain_trace_kernel<true, false, true, 1, 1>)
-                 : (f ? chain_trace_kernel<false, true, true, 1, 1> : chain_trace_kernel<false, false, true, 1, 1>);
-    if (inst && step == 2)
-        return c ? (f ? chain_trace_kernel<true, true, true, 1, 2> : chain_trace_kernel<true, false, true, 1, 2>)
-                 : (f ? chain_trace_kernel<false, true, true, 1, 2> : chain_trace_kernel<false, false, true, 1, 2>);
-    if (inst) return c ? (f ? chain_trace_kernel<true, true, true> : chain_trace_kernel<true, false, true>)
-                       : (f ? chain_trace_kernel<false, true, true> : chain_trace_kernel<false, false, true>);
-    return c ? (f ? chain_trace_kernel<true, true, false> : chain_trace_kernel<true, false, false>)
-             : (f ? chain_trace_kernel<false, true, false> : chain_trace_kernel<false, false, false>);
+        return with_bools([](auto F) -> KernelFn { return chain_trace_kernel<false, F(), false, 8>; }, f);
+    if (inst) return with_ints<1, 2, 0>(step, [&](auto S) {
+        return with_bools([](auto C, auto F) -> KernelFn { return chain_trace_kernel<C(), F(), true, 1, decltype(S)::value>; }, c, f);
+    });
+    return with_bools([](auto C, auto F) -> KernelFn { return chain_trace_kernel<C(), F(), false>; }, c, f);
 }
 KernelFn pick_unit_eye(bool c, bool f, bool inst) {
-    if (inst) return c ? (f ? unit_eye_kernel<true, true, true> : unit_eye_kernel<true, false, true>)
-                       : (f ? unit_eye_kernel<false, true, true> : unit_eye_kernel<false, false, true>);
-    if (!c) return f ? unit_eye_kernel<false, true, false, 7> : unit_eye_kernel<false, false, false, 7>;
-    return f ? unit_eye_kernel<true, true, false> : unit_eye_kernel<true, false, false>;
+    if (inst) return with_bools([](auto C, auto F) -> KernelFn { return unit_eye_kernel<C(), F(), true>; }, c, f);
+    if (!c) return with_bools([](auto F) -> KernelFn { return unit_eye_kernel<false, F(), false, 7>; }, f);
+    return with_bools([](auto F) -> KernelFn { return unit_eye_kernel<true, F(), false>; }, f);
 }
 KernelFn pick_chain_compact() { return chain_compact_kernel; }
 KernelFn pick_chain_merge() { return chain_merge_kernel; }
-template <bool C, bool R = false>
-static KernelFn chain_fallback_fn(bool po, bool inst, int rec) {
-    if (rec == 2) return po ? (inst ? chain_fallback_kernel<true, true, 2, C, R> : chain_fallback_kernel<true, false, 2, C, R>)
-                            : (inst ? chain_fallback_kernel<false, true, 2, C, R> : chain_fallback_kernel<false, false, 2, C, R>);
-    return po ? (inst ? chain_fallback_kernel<true, true, 1, C, R> : chain_fallback_kernel<true, false, 1, C, R>)
-              : (inst ? chain_fallback_kernel<false, true, 1, C, R> : chain_fallback_kernel<false, false, 1, C, R>);
-}
 KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count, bool rays) {
-    if (rays) return count ? chain_fallback_fn<true, true>(po, inst, rec) : chain_fallback_fn<false, true>(po, inst, rec);
-    return count ? chain_fallback_fn<true>(po, inst, rec) : chain_fallback_fn<false>(po, inst, rec);
+    return with_bools([](auto R, auto C, auto REC2, auto PO, auto I) -> KernelFn {
+        return chain_fallback_kernel<PO(), I(), REC2() ? 2 : 1, C(), R()>;
+    }, rays, count, rec == 2, po, inst);
 }
 KernelFn pick_chain_finish(bool rays) { return rays ? chain_finish_kernel<true> : chain_finish_kernel<false>; }
 KernelFn pick_chain_fold() { return chain_fold_kernel; }

@@ -93,7 +93,9 @@ __global__ void __launch_bounds__(kWG, MINW) shadow_kernel(RenderParams P, size_
         const DRay r = make_ray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), d.w);
         DHit h{o.w, 0.f, 0.f, -1};
         const uint32_t n0 = st.nodes;
-        P.occl[e] = traverse<true, COUNT, FAST, INST, CHECK, false, !INST>(T, r, 0.001f, h, st) ? 1 : 0;
+        constexpr uint32_t ANYHIT = W_ANY | walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) |
+                                    walk_opt(W_NOCHECK, !CHECK) | walk_opt(W_XONE, !INST);
+        P.occl[e] = traverse<ANYHIT>(T, r, 0.001f, h, st) ? 1 : 0;
         return st.nodes - n0;
     };
     // per-XCD band of ray slots and its chunk counter (own 128-B line)
@@ -237,7 +239,7 @@ __global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DL
     for (size_t i = (size_t)blockIdx.x * kWG + tid; i < n; i += (size_t)gridDim.x * kWG) {
         DRay r = make_ray(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
         DHit h{tmax[i], 0.f, 0.f, -1};
-        bool hit = traverse<ANY, false, false, INST>(T, r, tmin[i], h, st);
+        bool hit = traverse<walk_opt(W_ANY, ANY) | walk_opt(W_INST, INST)>(T, r, tmin[i], h, st);
         mrt_hit res;
         res.t = h.t; res.a = h.a; res.b = h.b; res.prim = hit ? (ANY ? 0 : h.prim) : -1;
         res.inst = (hit && !ANY) ? h.inst : -1;
@@ -514,76 +516,45 @@ static int blocks_per_cu(KernelFn f, size_t lds) {
     return n;
 }
 
-template <int W, bool I = false, bool CHK = true, bool X = false>
+template <int W, bool I, bool CHK = true, bool X = false>
 static KernelFn primary_fn(bool c, bool f) {
-    return c ? (f ? primary_kernel<true, W, true, I, CHK, X> : primary_kernel<true, W, false, I, CHK, X>)
-             : (f ? primary_kernel<false, W, true, I, CHK, X> : primary_kernel<false, W, false, I, CHK, X>);
+    return with_bools([](auto C, auto F) -> KernelFn { return primary_kernel<C(), W, F(), I, CHK, X>; }, c, f);
 }
 // check: the special-leaf scene has alpha-mapped or motion-blurred lanes; scenes with
 // instances only take the variants without those tests (no noinline calls: C5's nested
 // instance walk at 5 waves spills 28 B instead of 256 B per lane)
 // xone: the one-exit walk loop (non-instanced scenes; the instanced walk keeps its exits:
 // C5's primary launch measured 36% slower with one)
-static KernelFn pick_primary(int w, bool c, bool f, bool inst, bool check = true, bool xone = false) {
-    if (inst && !check) {
-        switch (g_tune.primary_inst_waves) {
-            case 4: return primary_fn<4, true, false>(c, f);
-            case 6: return primary_fn<6, true, false>(c, f);
-            case 1: return primary_fn<1, true, false>(c, f);
-            default: return primary_fn<5, true, false>(c, f);
-        }
-    }
-    if (inst) {   // special-leaf scenes (instances: nested BLAS walks)
-        switch (g_tune.primary_inst_waves) {
-            case 4: return primary_fn<4, true>(c, f);   // 128 VGPRs: the nested instance walk without spills
-            case 5: return primary_fn<5, true>(c, f);
-            case 6: return primary_fn<6, true>(c, f);
-            default: return primary_fn<1, true>(c, f);
-        }
-    }
-    if (xone) {
-        switch (w) {
-            case 6: return primary_fn<6, false, true, true>(c, f);
-            case 7: return primary_fn<7, false, true, true>(c, f);
-            case 8: return primary_fn<8, false, true, true>(c, f);
-            default: return primary_fn<1, false, true, true>(c, f);
-        }
-    }
-    switch (w) {
-        case 6: return primary_fn<6>(c, f);
-        case 7: return primary_fn<7>(c, f);
-        case 8: return primary_fn<8>(c, f);
-        default: return primary_fn<1>(c, f);
-    }
+KernelFn pick_primary(int w, int inst_waves, bool c, bool f, bool inst, bool check, bool xone) {
+    if (inst && !check) return with_ints<4, 6, 1, 5>(inst_waves, [&](auto W) { return primary_fn<W(), true, false>(c, f); });
+    // special-leaf scenes (instances: nested BLAS walks); 4 waves: 128 VGPRs, the nested instance walk without spills
+    if (inst) return with_ints<4, 5, 6, 1>(inst_waves, [&](auto W) { return primary_fn<W(), true>(c, f); });
+    if (xone) return with_ints<6, 7, 8, 1>(w, [&](auto W) { return primary_fn<W(), false, true, true>(c, f); });
+    return with_ints<6, 7, 8, 1>(w, [&](auto W) { return primary_fn<W(), false>(c, f); });
 }
+// kGen / kResolve: no traversal, FAST unused; special-leaf scenes take POINT_ONLY = false
 // bound: the dome-light resolve pass at 4 waves (~240 VGPRs unbounded)
 template <int MODE>
-static KernelFn shade_mode_fn(bool c, bool po, bool inst, bool bound = false) {   // kGen / kResolve: no traversal, FAST unused
-    if (!c && MODE == kResolve && bound) {
+static KernelFn shade_mode_fn(bool c, bool po, bool inst, bool bound) {
+    if (!c && MODE == kResolve && bound)
         // special-leaf scenes at 3 waves: 168 VGPRs and no scratch (152 B / 40 spills at 4 waves);
         // C5's resolve pass -0.7% (profiles/r06_c5_resolve_waves_ab.txt)
-        if (inst) return shade_kernel<false, false, false, true, MODE, 0, 3>;
-        return po ? shade_kernel<false, true, false, false, MODE, 0, 4> : shade_kernel<false, false, false, false, MODE, 0, 4>;
-    }
-    if (inst) return c ? shade_kernel<true, false, false, true, MODE> : shade_kernel<false, false, false, true, MODE>;
-    if (po) return c ? shade_kernel<true, true, false, false, MODE> : shade_kernel<false, true, false, false, MODE>;
-    return c ? shade_kernel<true, false, false, false, MODE> : shade_kernel<false, false, false, false, MODE>;
+        return with_bools([](auto I, auto PO) -> KernelFn {
+            return shade_kernel<false, PO() && !I(), false, I(), MODE, 0, I() ? 3 : 4>;
+        }, inst, po);
+    return with_bools([](auto I, auto PO, auto C) -> KernelFn { return shade_kernel<C(), PO() && !I(), false, I(), MODE>; }, inst, po, c);
 }
-using ShadowFn = void (*)(RenderParams, size_t, int, int);
 // MINW: launch-bounds occupancy target of the timed (COUNT = false) variants
 template <bool INST, bool REFILL, bool CHECK, int MINW = 1>
 static ShadowFn shadow_fn(bool c, bool f) {
-    return c ? (f ? shadow_kernel<true, true, INST, REFILL, CHECK> : shadow_kernel<true, false, INST, REFILL, CHECK>)
-             : (f ? shadow_kernel<false, true, INST, REFILL, CHECK, MINW> : shadow_kernel<false, false, INST, REFILL, CHECK, MINW>);
+    return with_bools([](auto C, auto F) -> ShadowFn { return shadow_kernel<C(), F(), INST, REFILL, CHECK, C() ? 1 : MINW>; }, c, f);
 }
-template <bool INST, bool REFILL, bool CHECK>
-static ShadowFn shadow_fn_w(bool c, bool f) { return shadow_fn<INST, REFILL, CHECK, 8>(c, f); }
 // check: the scene has alpha-mapped or motion-blurred lanes (child-word bit 3), which the
 // refill step must test as such
-static ShadowFn pick_shadow(bool c, bool f, bool inst, bool refill, bool check) {
-    if (!refill) return inst ? shadow_fn<true, false, true>(c, f) : shadow_fn_w<false, false, false>(c, f);
-    if (!inst) return shadow_fn_w<false, true, false>(c, f);
-    return check ? shadow_fn<true, true, true>(c, f) : shadow_fn_w<true, true, false>(c, f);
+ShadowFn pick_shadow(bool c, bool f, bool inst, bool refill, bool check) {
+    if (!refill) return inst ? shadow_fn<true, false, true>(c, f) : shadow_fn<false, false, false, 8>(c, f);
+    if (!inst) return shadow_fn<false, true, false, 8>(c, f);
+    return check ? shadow_fn<true, true, true>(c, f) : shadow_fn<true, true, false, 8>(c, f);
 }
 // shadow rays per pixel at most: num_paths x (1 per point light, m_numSamples per area / dome light)
 static int max_shadow_rays(const Scene& s) {
@@ -592,10 +563,14 @@ static int max_shadow_rays(const Scene& s) {
     return s.num_paths * per_path;
 }
 
-// rec: Shader REC (0 direct, 1 reflection / refraction chains, 2 + path tracing)
-static KernelFn pick_shade(bool c, bool po, bool f, bool inst, int rec) {
+KernelFn pick_shade(bool c, bool po, bool f, bool inst, int rec) {
     if (rec) return pick_shade_rec(c, po, f, inst, rec);
-    return pick4<ShadeK, 0>(c, po, f, inst);
+    return shade_fn<0>(c, po, f, inst);
+}
+// the wavefront shadow passes 2a (gen) / 2c (resolve)
+KernelFn pick_shade_mode(bool resolve, bool c, bool po, bool inst, bool bound) {
+    if (!resolve) return shade_mode_fn<kGen>(c, po, inst, bound);
+    return shade_mode_fn<kResolve>(c, po, inst, bound);
 }
 
 // The wavefront chain engine (mrt_chain.hip) for the shading of a REC scene:
@@ -1035,7 +1010,7 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
     const bool chk = d.has_alpha || d.has_mb;
     const bool rays = P.mode == 2;   // a ray batch: the kernels' ray-mode instantiations
     if ((rc = launch(rays ? pick_primary_rays(count, fb, inst, chk, g_tune.walk_exit == 1)
-                          : pick_primary(g_tune.primary_waves, count, fb, inst, chk, g_tune.walk_exit == 1))))
+                          : pick_primary(g_tune.primary_waves, g_tune.primary_inst_waves, count, fb, inst, chk, g_tune.walk_exit == 1))))
         return rc;
     HIP_OK(hipEventRecord(c.evm, stream));
     P.queue = qbase + 8 * 32;
@@ -1070,7 +1045,8 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
             P.ray_e = c.ray_e;
             P.lrec = c.lrec;
         }
-        if ((rc = launch(rays ? pick_shade_mode_rays(false, count, d.point_only, inst) : shade_mode_fn<kGen>(count, d.point_only, inst))))
+        if ((rc = launch(rays ? pick_shade_mode_rays(false, count, d.point_only, inst)
+                              : pick_shade_mode(false, count, d.point_only, inst, false))))
             return rc;
         // lane refill for dome-light (incoherent) rays: D1 -7%, C5 -13% shade pass; coherent
         // area-light rays keep the bands (C4: refill +9%)
@@ -1112,7 +1088,7 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
         P.queue = qbase + 16 * 32;
         // dome-light resolve passes run faster at 4 waves (D1 -4%, C5 -1.2 ms), the rect-light one not (C4 +2%)
         if ((rc = launch(rays ? pick_shade_mode_rays(true, count, d.point_only, inst)
-                              : shade_mode_fn<kResolve>(count, d.point_only, inst, dome))))
+                              : pick_shade_mode(true, count, d.point_only, inst, dome))))
             return rc;
         P.ray_e = nullptr;
         P.lrec = nullptr;

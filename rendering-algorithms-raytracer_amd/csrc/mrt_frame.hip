@@ -68,7 +68,9 @@ __device__ __forceinline__ v3 shade1_hit(const RenderParams& P, const Trav& T, T
             const DRay sr = make_ray(from, L);
             DHit sh{distance, 0.f, 0.f, -1};
             shadow_total++;
-            if (traverse<true, COUNT, FAST, false, true, WALK == 2, WALK != 0, false, true>(T, sr, 0.001f, sh, st)) attenuate = 0.0f;
+            constexpr uint32_t ANYHIT = W_ANY | walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_LN, WALK == 2) |
+                                        walk_opt(W_XONE, WALK != 0) | W_OROWS;
+            if (traverse<ANYHIT>(T, sr, 0.001f, sh, st)) attenuate = 0.0f;
         }
         attenuate *= nDotL;
         spec = rdl * attenuate;
@@ -145,10 +147,10 @@ __global__ void __launch_bounds__(kWG, MINW) shade1_kernel(RenderParams P) {
 // LN: the hierarchy's top kLdsNodes nodes are staged in LDS (+8 KB per workgroup)
 // and both walks read their wave-uniform visits from there (traverse_impl); the
 // host runs it when asked (tuning "lds_nodes").
-// WALK (traverse_impl): 0 the walk loop with a second exit (stack overflow returns), 1 one
-// exit (XONE), 2 one exit + LN, 3 one exit and one latch (OL) for the camera rays' walk.
-// Same bits either way; the host runs 3 unless tuned (walk_exit, walk_latch, lds_nodes).
-// Both walks fetch wave-uniform nodes through the wave's octant rows (traverse_impl, OROWS).
+// WALK (the walk options of mrt_kernels.h): 0 the walk loop with a second exit (stack overflow
+// returns), 1 one exit (W_XONE), 2 one exit + W_LN, 3 one exit and one latch (W_OL) for the camera
+// rays' walk.  Same bits either way; the host runs 3 unless tuned (walk_exit, walk_latch, lds_nodes).
+// Both walks fetch wave-uniform nodes through the wave's octant rows (W_OROWS).
 template <bool COUNT, bool FAST, int MINW, bool POW, int WALK = 1>
 __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
     constexpr bool LN = WALK == 2;
@@ -188,7 +190,9 @@ __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
             const EyeRay er = camera_ray(PA.cam[f], PA.seed + (uint32_t)f, x, y, rsqT);
             const DRay r = make_ray(er.o, er.d);
             DHit h{1e12f, 0.f, 0.f, -1};
-            const bool hit = traverse<false, COUNT, FAST, false, true, LN, WALK != 0, WALK == 3, true>(T, r, 0.001f, h, st);
+            constexpr uint32_t CLOSEST = walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_LN, LN) |
+                                         walk_opt(W_XONE, WALK != 0) | walk_opt(W_OL, WALK == 3) | W_OROWS;
+            const bool hit = traverse<CLOSEST>(T, r, 0.001f, h, st);
             const RenderParams& PB = reload_params();   // shading parameters
             v3 col = mk(PB.bg[0], PB.bg[1], PB.bg[2]);
             if (hit) {
@@ -224,40 +228,25 @@ __global__ void __launch_bounds__(kWG, MINW) frame1_kernel(RenderParams P) {
     flush_stats<COUNT, false, false>(P, ss, shadow_total, lane_id(), t0, ntiles, 0, wave);
 }
 
-template <int W, bool POW, bool R = false>
+template <int W, bool POW, bool R>
 static KernelFn shade1_fn(bool c, bool f) {
-    return c ? (f ? shade1_kernel<true, true, W, POW, R> : shade1_kernel<true, false, W, POW, R>)
-             : (f ? shade1_kernel<false, true, W, POW, R> : shade1_kernel<false, false, W, POW, R>);
+    return with_bools([](auto C, auto F) -> KernelFn { return shade1_kernel<C(), F(), W, POW, R>; }, c, f);
 }
 template <int W, bool POW, int WALK>
 static KernelFn frame1_fn(bool c, bool f) {
-    return c ? (f ? frame1_kernel<true, true, W, POW, WALK> : frame1_kernel<true, false, W, POW, WALK>)
-             : (f ? frame1_kernel<false, true, W, POW, WALK> : frame1_kernel<false, false, W, POW, WALK>);
-}
-template <int WALK>
-static KernelFn pick_frame1_walk(int w, bool c, bool f, bool pow) {
-    if (pow) return w == 1 ? frame1_fn<1, true, WALK>(c, f) : frame1_fn<6, true, WALK>(c, f);
-    switch (w) {
-        case 1: return frame1_fn<1, false, WALK>(c, f);
-        case 5: return frame1_fn<5, false, WALK>(c, f);
-        case 7: return frame1_fn<7, false, WALK>(c, f);
-        case 8: return frame1_fn<8, false, WALK>(c, f);
-        default: return frame1_fn<6, false, WALK>(c, f);
-    }
+    return with_bools([](auto C, auto F) -> KernelFn { return frame1_kernel<C(), F(), W, POW, WALK>; }, c, f);
 }
 // pow: a Blinn material with specExp != 1 (those scenes run at 6 waves, or unbounded);
 // walk: 0 two-exit walk loop, 1 one exit, 2 one exit + the LDS top-node walk, 3 one exit + one latch
 KernelFn pick_frame1(int w, bool c, bool f, bool pow, int walk) {
-    switch (walk) {
-        case 0: return pick_frame1_walk<0>(w, c, f, pow);
-        case 2: return pick_frame1_walk<2>(w, c, f, pow);
-        case 3: return pick_frame1_walk<3>(w, c, f, pow);
-        default: return pick_frame1_walk<1>(w, c, f, pow);
-    }
+    return with_ints<0, 2, 3, 1>(walk, [&](auto WALK) {
+        constexpr int WK = decltype(WALK)::value;
+        if (pow) return with_ints<1, 6>(w, [&](auto W) { return frame1_fn<W(), true, WK>(c, f); });
+        return with_ints<1, 5, 7, 8, 6>(w, [&](auto W) { return frame1_fn<W(), false, WK>(c, f); });
+    });
 }
 // (the two-launch path: fused = 0, or a caller that wants hit records) at 5 waves
 KernelFn pick_shade1(bool c, bool f, bool pow, bool rays) {
-    if (rays) return pow ? shade1_fn<5, true, true>(c, f) : shade1_fn<5, false, true>(c, f);
-    return pow ? shade1_fn<5, true>(c, f) : shade1_fn<5, false>(c, f);
+    return with_bools([&](auto R, auto POW) { return shade1_fn<5, POW(), R()>(c, f); }, rays, pow);
 }
 }  // namespace mrt

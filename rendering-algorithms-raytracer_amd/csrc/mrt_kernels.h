@@ -430,31 +430,75 @@ __device__ __forceinline__ bool tri_test_lane(const Trav& c, uint32_t toff, cons
     return ok != 0;
 }
 
-template <bool ANY, bool COUNT, bool FAST, bool INST = false, bool BL = false, bool CHECK = true, bool LN = false,
-          bool XONE = true, bool OL = false, bool OROWS = false>
+// The walk's compile-time options: one mask W of these flags, named at every call site
+// (traverse<W_ANY | walk_opt(W_COUNT, COUNT) | ...>).  No flag: a closest-hit walk of a plain
+// scene, exact box tests, the two-exit loop with the nested loop end.
+enum : uint32_t {
+    W_ANY = 1u << 0,     // any-hit (a shadow ray): the first accepted hit ends the walk
+    W_COUNT = 1u << 1,   // count mode: node / leaf visit statistics in TravStats
+    // the node boxes are known finite: the hardware min / max slab test for rays whose origin
+    // and 1/d are finite; any other ray takes the exact loop (traverse chooses per ray)
+    W_FAST = 1u << 2,
+    // leaf packets with ProxyObject lanes (child-word bit 2) intersect those lanes first, in
+    // lane order (intersect4, src/BVH.cpp:1305-1315), each through a nested BLAS traversal
+    // (proxy_hit); root / sp0 start such a nested walk
+    W_INST = 1u << 3,
+    // a BLAS walk (proxy_hit only).  W_INST / W_BL walks test alpha-mapped lanes in packets
+    // with the check bit (3) -- and, in the world, motion-blurred ones
+    W_BL = 1u << 4,
+    // the scene has no alpha-mapped or motion-blurred lanes (no check bit is set), so their
+    // tests -- calls of the noinline mb_tri_test / alpha_rejects, whose call ABI costs the
+    // walk registers and scratch -- are compiled out (CHECK = false in the walk)
+    W_NOCHECK = 1u << 5,
+    // wave-uniform visits of the hierarchy's top nodes (index < kLdsNodes, renumbered breadth
+    // first on upload) read them from LDS (c.lnodes, one broadcast address) instead of the
+    // scalar cache -- faster where the top levels end most rays (tuning lds_nodes, off by
+    // default: mrt_device.h)
+    W_LN = 1u << 6,
+    // the one-exit walk loop: a stack overflow raises the launch's counter itself (Trav::ovf)
+    // instead of returning -- frame1_kernel, primary_kernel and the shadow and adaptive kernels
+    // of plain scenes (C4 -6%, A3 -4%); off in the chain engine (P4 +21%, R3 +4% with it) and
+    // in nested BLAS walks (C5's primary launch measured 37% slower with it)
+    W_XONE = 1u << 7,
+    // the one-latch loop end -- the closest-hit walks of primary_kernel and the adaptive kernel
+    // of plain scenes, and frame1_kernel's unless the host picks the nested form (tuning
+    // walk_latch 0); any-hit walks and the chain engine keep the nested form (round 6 A/B,
+    // DESIGN §4)
+    W_OL = 1u << 8,
+    // a wave whose rays share an octant fetches a wave-uniform node's six box rows in near /
+    // far order through per-walk row offsets (oct_rows), so its scalar-node step runs the one
+    // box_test_oct<0> body without choosing among the octants' copies; waves of mixed octants
+    // test the node as it lies.  frame1_kernel's walks only: in the shader kernels
+    // (Shader::occluded) the fetched rows are not all in scalar registers, which pin_rows
+    // needs (the compiler rejects it there), so the other walks keep the per-step choice
+    W_OROWS = 1u << 9,
+};
+constexpr uint32_t walk_opt(uint32_t flag, bool on) { return on ? flag : 0u; }
+
+template <uint32_t W>
 __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st, int32_t root = 0,
                               int sp0 = 0, int32_t aoff = 0);
 
 // One ProxyObject lane: its BLAS traversed with the object-space ray, the
 // current t as tMax, on the same stack above the caller's entries.
-template <bool ANY, bool COUNT, bool FAST, bool CHECK = true>
+// (W: the world walk's options)
+template <uint32_t W>
 __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r, float tMin, DHit& h,
                                           TravStats& st, int sp) {
     const DevInstance& I = c.inst[inst];
     const DRay ro = object_ray(I, r, c.rcpT);
     // BLAS packets with alpha-mapped triangles (check bit): PrimShade = shade_base + BLAS object
-    // (the nested walk keeps the two-exit loop: C5's primary launch measured 37% slower with
-    // one exit, traverse_impl XONE)
-    if (FAST && ro.finite)
-        return traverse_impl<ANY, COUNT, true, false, true, CHECK, false, false>(c, ro, tMin, h, st, I.root, sp, I.shade_base);
-    return traverse_impl<ANY, COUNT, false, false, true, CHECK, false, false>(c, ro, tMin, h, st, I.root, sp, I.shade_base);
+    // (the nested walk keeps the two-exit loop, W_XONE)
+    constexpr uint32_t BLAS = (W & (W_ANY | W_COUNT | W_NOCHECK)) | W_BL;
+    if ((W & W_FAST) && ro.finite) return traverse_impl<BLAS | W_FAST>(c, ro, tMin, h, st, I.root, sp, I.shade_base);
+    return traverse_impl<BLAS>(c, ro, tMin, h, st, I.root, sp, I.shade_base);
 }
 
 // BVH::intersect, QBVH branch (src/BVH.cpp:1128-1178).  Returns hit; h.prim is
 // then the packed triangle slot (leaf << 2 | k), resolved by traverse().  On a
 // stack overflow the query is abandoned and the event reported: a two-exit walk
 // sets st.overflow and returns (its kernel's epilogue raises the launch's counter),
-// a one-exit walk (XONE) raises the counter itself (Trav::ovf) and carries no flag.
+// a one-exit walk (W_XONE) raises the counter itself (Trav::ovf) and carries no flag.
 // The caller enters with h.prim == -1: a closest-hit walk keeps no hit flag (a
 // loop-carried bool is a lane mask, re-formed at every merge point of the two
 // divergent loops on the scalar unit); every accept stores a packed slot >= 0
@@ -468,27 +512,12 @@ __device__ __forceinline__ bool proxy_hit(const Trav& c, int inst, const DRay& r
 // of one packet loop per slot.  Same visit order and same t at every box test
 // as the reference.
 //
-// INST: leaf packets with ProxyObject lanes (child-word bit 2) intersect those
-// lanes first, in lane order (intersect4, src/BVH.cpp:1305-1315), each through
-// a nested BLAS traversal (proxy_hit); root / sp0 start such a nested walk.
-// INST / BL (a BLAS walk): packets with the check bit (3) test alpha-mapped
-// lanes -- and, in the world, motion-blurred ones.
-// CHECK = false: the scene has no alpha-mapped or motion-blurred lanes (no check bit
-// is set), so their tests -- calls of the noinline mb_tri_test / alpha_rejects, whose
-// call ABI costs the walk registers and scratch -- are compiled out.
-// LN: wave-uniform visits of the hierarchy's top nodes (index < kLdsNodes, renumbered
-// breadth first on upload) read them from LDS (c.lnodes, one broadcast address)
-// instead of the scalar cache -- faster where the top levels end most rays (tuning
-// lds_nodes, off by default: mrt_device.h).
-// OROWS: a wave whose rays share an octant fetches a wave-uniform node's six box rows
-// in near / far order through per-walk row offsets (oct_rows), so its scalar-node step
-// runs the one box_test_oct<0> body without choosing among the octants' copies; waves
-// of mixed octants test the node as it lies.  frame1_kernel's walks only: in the shader
-// kernels (Shader::occluded) the fetched rows are not all in scalar registers, which
-// pin_rows needs (the compiler rejects it there), so the other walks keep the per-step choice.
-template <bool ANY, bool COUNT, bool FAST, bool INST, bool BL, bool CHECK, bool LN, bool XONE, bool OL, bool OROWS>
+// The options W (W_ANY ... W_OROWS above) are the body's constants ANY ... OROWS.
+template <uint32_t W>
 __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st, int32_t root,
                               int sp0, int32_t aoff) {
+    constexpr bool ANY = W & W_ANY, COUNT = W & W_COUNT, FAST = W & W_FAST, INST = W & W_INST, BL = W & W_BL,
+                   CHECK = !(W & W_NOCHECK), LN = W & W_LN, XONE = W & W_XONE, OL = W & W_OL, OROWS = W & W_OROWS;
     int sp = sp0;
     int32_t cur = root;
     // octant-ordered box tests (box_test_oct) when every active lane's ray has the same
@@ -641,7 +670,7 @@ __device__ bool traverse_impl(const Trav& c, const DRay& r, float tMin, DHit& h,
                             const int32_t pm = c.leaves[leaf].prim[j];
                             if (pm > -2) continue;  // a triangle lane
                             DHit hi{h.t, 0.f, 0.f, -1};
-                            const bool ph = proxy_hit<ANY, COUNT, FAST, CHECK>(c, -2 - pm, r, tMin, hi, st, sp);
+                            const bool ph = proxy_hit<W>(c, -2 - pm, r, tMin, hi, st, sp);
                             if (st.overflow) return !ANY && h.prim >= 0;
                             if (ph) {
                                 if (ANY) return true;
@@ -893,23 +922,15 @@ __device__ __forceinline__ bool anyhit_step_inst(const Trav& c, float tMin, floa
     return false;
 }
 
-// FAST (node boxes known finite) uses the hardware min/max slab test for rays
-// whose origin and 1/d are finite; any other ray takes the exact loop.  A
-// closest hit's packed slot is resolved to the global prim id here.
+// One ray's walk with the options W (W_ANY ... W_OROWS; W_BL is proxy_hit's): the W_FAST
+// form for rays whose origin and 1/d are finite, the exact loop (which has no W_LN / W_OROWS
+// form) for any other.  A closest hit's packed slot is resolved to the global prim id here.
 // An instance hit's id is the instance's hit_base + its BLAS object index.
-// XONE: the one-exit walk loop (traverse_impl) -- frame1_kernel, primary_kernel and the
-// shadow and adaptive kernels of plain scenes (C4 -6%, A3 -4%); off in the chain engine
-// (P4 +21%, R3 +4% with it) and nested BLAS walks.
-// OL: the one-latch loop end (traverse_impl) -- the closest-hit walks of primary_kernel and
-// the adaptive kernel of plain scenes, and frame1_kernel's unless the host picks the nested
-// form (tuning walk_latch 0); any-hit walks and the chain engine keep the nested form
-// (round 6 A/B).
-// OROWS: scalar node fetches through the wave's octant rows (traverse_impl) -- frame1_kernel's walks.
-template <bool ANY, bool COUNT, bool FAST = false, bool INST = false, bool CHECK = true, bool LN = false,
-          bool XONE = false, bool OL = false, bool OROWS = false>
+template <uint32_t W>
 __device__ __forceinline__ bool traverse(const Trav& c, const DRay& r, float tMin, DHit& h, TravStats& st) {
-    const bool hit = (FAST && r.finite) ? traverse_impl<ANY, COUNT, true, INST, false, CHECK, LN, XONE, OL, OROWS>(c, r, tMin, h, st)
-                                        : traverse_impl<ANY, COUNT, false, INST, false, CHECK, false, XONE, OL>(c, r, tMin, h, st);
+    constexpr bool ANY = W & W_ANY, INST = W & W_INST;
+    const bool hit = ((W & W_FAST) && r.finite) ? traverse_impl<W | W_FAST>(c, r, tMin, h, st)
+                                                : traverse_impl<W & ~(W_FAST | W_LN | W_OROWS)>(c, r, tMin, h, st);
     if (!ANY && hit) {
         h.prim = c.leaves[(uint32_t)h.prim >> 2].prim[h.prim & 3];
         if (INST && h.inst >= 0) h.prim += c.inst[h.inst].hit_base;

@@ -13,8 +13,7 @@ namespace mrt {
 // special-leaf scenes): the targets are a tuning matter, every variant gives the same bits.
 template <int W, bool I, bool CHK, bool X>
 static KernelFn primary_rays_fn(bool c, bool f) {
-    return c ? (f ? primary_kernel<true, W, true, I, CHK, X, true> : primary_kernel<true, W, false, I, CHK, X, true>)
-             : (f ? primary_kernel<false, W, true, I, CHK, X, true> : primary_kernel<false, W, false, I, CHK, X, true>);
+    return with_bools([](auto C, auto F) -> KernelFn { return primary_kernel<C(), W, F(), I, CHK, X, true>; }, c, f);
 }
 KernelFn pick_primary_rays(bool c, bool f, bool inst, bool check, bool xone) {
     if (inst) return check ? primary_rays_fn<5, true, true, false>(c, f) : primary_rays_fn<5, true, false, false>(c, f);
@@ -23,17 +22,15 @@ KernelFn pick_primary_rays(bool c, bool f, bool inst, bool check, bool xone) {
 
 // fused shading (direct lighting, or rec 1 / 2: the chains traced inline)
 KernelFn pick_shade_rays(bool c, bool po, bool f, bool inst, int rec) {
-    if (rec == 2) return pick4<ShadeRaysK, 2>(c, po, f, inst);
-    if (rec == 1) return pick4<ShadeRaysK, 1>(c, po, f, inst);
-    return pick4<ShadeRaysK, 0>(c, po, f, inst);
+    return with_ints<2, 1, 0>(rec, [&](auto REC) { return shade_fn<REC(), true>(c, po, f, inst); });
 }
 
 // wavefront shadow passes 2a (gen) / 2c (resolve): no traversal, FAST unused
 template <int MODE>
 static KernelFn shade_mode_rays_fn(bool c, bool po, bool inst) {
-    if (inst) return c ? shade_kernel<true, false, false, true, MODE, 0, 1, true> : shade_kernel<false, false, false, true, MODE, 0, 1, true>;
-    if (po) return c ? shade_kernel<true, true, false, false, MODE, 0, 1, true> : shade_kernel<false, true, false, false, MODE, 0, 1, true>;
-    return c ? shade_kernel<true, false, false, false, MODE, 0, 1, true> : shade_kernel<false, false, false, false, MODE, 0, 1, true>;
+    return with_bools([](auto I, auto PO, auto C) -> KernelFn {
+        return shade_kernel<C(), PO() && !I(), false, I(), MODE, 0, 1, true>;
+    }, inst, po, c);
 }
 KernelFn pick_shade_mode_rays(bool resolve, bool c, bool po, bool inst) {
     return resolve ? shade_mode_rays_fn<kResolve>(c, po, inst) : shade_mode_rays_fn<kGen>(c, po, inst);

@@ -6,29 +6,30 @@
 
 namespace mrt {
 
-template <bool C, bool PO, bool F, bool I, int REC>
-struct AdaptK { static constexpr KernelFn fn = adaptive_kernel<C, PO, F, I, REC>; };
-
 KernelFn pick_shade_rec(bool c, bool po, bool f, bool inst, int rec) {
-    if (rec == 2) return pick4<ShadeK, 2>(c, po, f, inst);
-    return pick4<ShadeK, 1>(c, po, f, inst);
+    return with_ints<2, 1>(rec, [&](auto REC) { return shade_fn<REC()>(c, po, f, inst); });
 }
 
+// (special-leaf scenes take POINT_ONLY = false, as shade_fn)
+template <int REC>
+static KernelFn adaptive_fn(bool c, bool po, bool f, bool inst) {
+    return with_bools([](auto I, auto PO, auto C, auto F) -> KernelFn {
+        return adaptive_kernel<C(), PO() && !I(), F(), I(), REC>;
+    }, inst, po, c, f);
+}
 // direct-lighting adaptive kernels (timed variants) at an occupancy target:
 // unbounded, the compiler gives them all 256 VGPRs (one wave per SIMD)
-template <int W, int REC = 0>
+template <int W>
 static KernelFn adapt_direct(bool po, bool f, bool inst) {
-    if (inst) return f ? adaptive_kernel<false, false, true, true, REC, W> : adaptive_kernel<false, false, false, true, REC, W>;
-    if (po) return f ? adaptive_kernel<false, true, true, false, REC, W> : adaptive_kernel<false, true, false, false, REC, W>;
-    return f ? adaptive_kernel<false, false, true, false, REC, W> : adaptive_kernel<false, false, false, false, REC, W>;
+    return with_bools([](auto I, auto PO, auto F) -> KernelFn {
+        return adaptive_kernel<false, PO() && !I(), F(), I(), 0, W>;
+    }, inst, po, f);
 }
 
 KernelFn pick_adaptive(bool c, bool po, bool f, bool inst, int rec) {
     if (rec == 0 && !c) return adapt_direct<6>(po, f, inst);   // 4 / 5 waves measured 6% / 1% slower on A3
     // (REC 1 / 2 kernels bounded to 2 or 3 waves still end at one: no variants)
-    if (rec == 2) return pick4<AdaptK, 2>(c, po, f, inst);
-    if (rec == 1) return pick4<AdaptK, 1>(c, po, f, inst);
-    return pick4<AdaptK, 0>(c, po, f, inst);
+    return with_ints<2, 1, 0>(rec, [&](auto REC) { return adaptive_fn<REC()>(c, po, f, inst); });
 }
 
 }  // namespace mrt

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mrt_kernels.h"
+#include "mrt_pick.h"
 #include "mrt_scene.h"
 #include "mrt_texture.h"
 
@@ -336,7 +337,9 @@ struct Shader {
         } else {
             DRay r = make_ray(from, L, shadow_time);
             DHit h{tMax, 0.f, 0.f, -1};
-            return traverse<true, COUNT, FAST, INST, true, false, !INST>(T, r, 0.001f, h, st);
+            constexpr uint32_t ANYHIT = W_ANY | walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) |
+                                        walk_opt(W_XONE, !INST);
+            return traverse<ANYHIT>(T, r, 0.001f, h, st);
         }
     }
 
@@ -359,7 +362,7 @@ struct Shader {
             shadow_rays++;
             const DRay r = make_ray(o, L, shadow_time);
             DHit h{tb, 0.f, 0.f, -1};
-            if (!traverse<false, COUNT, FAST, INST>(T, r, 0.001f, h, st)) break;
+            if (!traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST)>(T, r, 0.001f, h, st)) break;
             int32_t ps_i = h.prim;
             if (INST && h.prim >= P.n_world) ps_i = inst_shade_index(h.prim, nullptr);
             const PrimShade ps = P.prims[ps_i];
@@ -993,7 +996,7 @@ struct Shader {
                 k = d;
             } else {
                 DHit h2{1e12f, 0.f, 0.f, -1};
-                if (traverse<false, COUNT, FAST, INST>(T, o.r2, 0.001f, h2, st)) {
+                if (traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST)>(T, o.r2, 0.001f, h2, st)) {
                     r = o.r2;
                     h = h2;
                     continue;
@@ -1025,7 +1028,7 @@ struct Shader {
                     const DRay c = disp_child(rec, k, i, cs, cam);
                     rec(6) = __int_as_float(++i);
                     DHit h2{1e12f, 0.f, 0.f, -1};
-                    if (traverse<false, COUNT, FAST, INST>(T, c, 0.001f, h2, st)) {
+                    if (traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST)>(T, c, 0.001f, h2, st)) {
                         r = c;
                         h = h2;
                         descend = true;
@@ -1356,7 +1359,9 @@ __global__ void __launch_bounds__(kWG, MINW) primary_kernel(RenderParams P) {
             const EyeRay er = source_ray<RAYS>(PA, cam, PA.seed + (uint32_t)f, x, y, rsqT);
             DRay r = make_ray(er.o, er.d, er.time);
             DHit h{1e12f, 0.f, 0.f, -1};
-            if (!traverse<false, COUNT, FAST, INST, CHECK, false, XONE, XONE && !INST>(T, r, 0.001f, h, st)) h.prim = -1;
+            constexpr uint32_t CLOSEST = walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) |
+                                         walk_opt(W_NOCHECK, !CHECK) | walk_opt(W_XONE, XONE) | walk_opt(W_OL, XONE && !INST);
+            if (!traverse<CLOSEST>(T, r, 0.001f, h, st)) h.prim = -1;
             const RenderParams& PC = reload_params();
             item_pixel<RAYS>(PC, item, lane_id(), x, y, slot);  // recompute: keeps it out of the traversal's live set
             PC.hits[slot] = make_float4(h.t, h.a, h.b, __int_as_float(h.prim));
@@ -1516,7 +1521,8 @@ __global__ void __launch_bounds__(kWG, MINW) adaptive_kernel(RenderParams P) {
         DHit h{1e12f, 0.f, 0.f, -1};
         v3 col;
         eye_rays++;
-        const bool hit = traverse<false, COUNT, FAST, INST, true, false, !INST, !INST>(T, r, 0.001f, h, st);
+        constexpr uint32_t CLOSEST = walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) | walk_opt(W_XONE | W_OL, !INST);
+        const bool hit = traverse<CLOSEST>(T, r, 0.001f, h, st);
         if (sample == 0) P.hits[slot] = make_float4(h.t, h.a, h.b, __int_as_float(hit ? h.prim : -1));
         if (hit) {
             eye_hits++;
@@ -1619,46 +1625,14 @@ __global__ void __launch_bounds__(kWG, MINW) adaptive_kernel(RenderParams P) {
     flush_stats<COUNT, false>(P, st, shadow_total, lane, t0, ntiles);
 }
 
-using KernelFn = void (*)(RenderParams);
-
-// K: a kernel family over <COUNT, POINT_ONLY, FAST, INST, REC> (ShadeK, AdaptK, ...)
-template <template <bool, bool, bool, bool, int> class K, int REC>
-static KernelFn pick4(bool c, bool po, bool f, bool inst) {
-    if (inst) return c ? (f ? K<true, false, true, true, REC>::fn : K<true, false, false, true, REC>::fn)
-                       : (f ? K<false, false, true, true, REC>::fn : K<false, false, false, true, REC>::fn);
-    if (po) return c ? (f ? K<true, true, true, false, REC>::fn : K<true, true, false, false, REC>::fn)
-                     : (f ? K<false, true, true, false, REC>::fn : K<false, true, false, false, REC>::fn);
-    return c ? (f ? K<true, false, true, false, REC>::fn : K<true, false, false, false, REC>::fn)
-             : (f ? K<false, false, true, false, REC>::fn : K<false, false, false, false, REC>::fn);
+// The fused shading kernel for a launch (mrt_pick.h; instantiated by the translation unit
+// that calls it: rec 0 mrt_device.hip, 1 / 2 mrt_rec.hip, ray mode mrt_rays.hip).
+// Special-leaf scenes take POINT_ONLY = false whatever their lights.
+template <int REC, bool RAYS = false>
+static KernelFn shade_fn(bool c, bool po, bool f, bool inst) {
+    return with_bools([](auto I, auto PO, auto C, auto F) -> KernelFn {
+        return shade_kernel<C(), PO() && !I(), F(), I(), kFused, REC, 1, RAYS>;
+    }, inst, po, c, f);
 }
-template <bool C, bool PO, bool F, bool I, int REC>
-struct ShadeK { static constexpr KernelFn fn = shade_kernel<C, PO, F, I, kFused, REC>; };
-template <bool C, bool PO, bool F, bool I, int REC>
-struct ShadeRaysK { static constexpr KernelFn fn = shade_kernel<C, PO, F, I, kFused, REC, 1, true>; };
-
-// defined in mrt_frame.hip: the one-point-light frame / shade kernels at an
-// occupancy target w; pow: a Blinn material with specExp != 1
-KernelFn pick_frame1(int w, bool c, bool f, bool pow, int walk);
-KernelFn pick_shade1(bool c, bool f, bool pow, bool rays = false);
-// defined in mrt_rec.hip: the fused chain kernels (rec 1: reflection / refraction,
-// 2: + path tracing) and the adaptive supersampling kernels (any rec)
-KernelFn pick_shade_rec(bool c, bool po, bool f, bool inst, int rec);
-KernelFn pick_adaptive(bool c, bool po, bool f, bool inst, int rec);
-// defined in mrt_chain.hip: the wavefront chain engine
-// (rays: the ray-mode instantiations -- the kernels that look at a unit's pixel or eye ray)
-KernelFn pick_chain0(bool resolve, bool po, bool inst, int rec, bool rays = false);
-KernelFn pick_chain_shade(bool resolve, bool po, bool inst, int rec, bool rays = false);
-KernelFn pick_chain_trace(bool c, bool f, bool inst, int step, bool rays = false);
-KernelFn pick_chain_compact();
-KernelFn pick_chain_merge();
-KernelFn pick_chain_fallback(bool po, bool inst, int rec, bool count, bool rays = false);
-KernelFn pick_chain_finish(bool rays = false);
-// defined in mrt_rays.hip: the ray-mode instantiations of the primary / shading kernels
-KernelFn pick_primary_rays(bool c, bool f, bool inst, bool check, bool xone);
-KernelFn pick_shade_rays(bool c, bool po, bool f, bool inst, int rec);
-KernelFn pick_shade_mode_rays(bool resolve, bool c, bool po, bool inst);
-KernelFn pick_chain_fold();
-KernelFn pick_unit_eye(bool c, bool f, bool inst);
-KernelFn pick_adapt_combine();
 
 }  // namespace mrt
