@@ -1008,6 +1008,20 @@ static void mesh_tangents(mesh_t* m) {
     }
 }
 
+/* the tangent frames of a mesh's normal slots (tan, btan: nn x 3 floats, either may be NULL);
+ * returns nn, 0 for a mesh without texture coordinates, -1 for a bad id */
+int oro_mesh_tangents(oro_scene* s, int mesh, float* tan, float* btan) {
+    if (mesh < 0 || mesh >= s->n_meshes) return -1;
+    mesh_t* m = &s->meshes[mesh];
+    mesh_tangents(m);
+    if (!m->tan) return 0;
+    for (int i = 0; i < m->nn; i++) {
+        if (tan) { tan[3 * i] = m->tan[i].x; tan[3 * i + 1] = m->tan[i].y; tan[3 * i + 2] = m->tan[i].z; }
+        if (btan) { btan[3 * i] = m->btan[i].x; btan[3 * i + 1] = m->btan[i].y; btan[3 * i + 2] = m->btan[i].z; }
+    }
+    return m->nn;
+}
+
 int oro_scene_build(oro_scene* s) {
     free_build(s);
     for (int i = 0; i < s->n_meshes; i++) mesh_tangents(&s->meshes[i]);

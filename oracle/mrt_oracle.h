@@ -11,13 +11,15 @@
  * never part of it: only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load it.
  *
- * PARITY UNPINNED against reference outputs: the reference cannot be compiled in
- * this image without stand-ins for headers the image lacks (<GL/glut.h>,
- * <Windows.h>; reference src/OpenGL.h:13, src/Scene.cpp:8) and it ships no tests,
- * golden images or fixtures.  What IS pinned: the x86 RCPSS/RSQRTSS emulation
- * (exhaustively, all 2^32 inputs, against live instructions), the OBJ-loader
- * scaling facts and the QBVH node/leaf counts measured from the reference in
- * SURVEY.md (tests/test_oracle_pins.py).
+ * PARITY: pinned to the reference's own code.  oracle/ref/ compiles the reference's
+ * sources (with stand-ins for <GL/glut.h> and <Windows.h>, which this image lacks) into a
+ * test driver; tests/test_reference_cpu.py compares this file with it bit for bit on the
+ * loader, the tree and its traversal, deterministic shading and replayed stochastic
+ * shading, and statistically where a frame spans chain levels; the driver's outputs are
+ * recorded under tests/golden/reference/.  Also pinned: the x86 RCPSS/RSQRTSS emulation
+ * (exhaustively, all 2^32 inputs, against live instructions) and the facts of
+ * tests/test_oracle_pins.py.  DESIGN.md ("Pinned to the reference") lists what still
+ * rests on this restatement alone.
  */
 #ifndef MRT_ORACLE_H
 #define MRT_ORACLE_H
@@ -160,6 +162,9 @@ int oro_scene_set_material_maps(oro_scene* s, int material, const int maps[6]);
 /* TriangleMesh m_texCoords (ntc x 2 floats) / m_texCoordIndices (nt x 3) of a mesh */
 int oro_mesh_set_texcoords(oro_scene* s, int mesh, int ntc, const float* uv, const uint32_t* tidx);
 int oro_mesh_texcoords(const oro_scene* s, int mesh, int* ntc, float* uv, uint32_t* tidx);
+/* TriangleMesh::preCalc's m_tangents / m_biTangents, one per normal slot (nn x 3 floats each;
+ * slots no triangle writes are zero).  Returns nn, 0 without texture coordinates, -1 = bad id */
+int oro_mesh_tangents(oro_scene* s, int mesh, float* tan, float* btan);
 /* MBObject (src/MBObject.cpp): every triangle of the mesh moves from its vertices
  * (time 0) to verts2 (time 1, nv x 3 floats) over the camera's time sample */
 int oro_mesh_set_motion(oro_scene* s, int mesh, const float* verts2);

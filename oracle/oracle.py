@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY.  Importable only from tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg.  The oracle is the checker, never the product.
-PARITY UNPINNED against reference outputs (see mrt_oracle.h).
+Parity with the reference's own code: tests/test_reference_cpu.py (see mrt_oracle.h).
 """
 from __future__ import annotations
 
@@ -130,6 +130,7 @@ def _declare(L):
     L.oro_scene_set_material_maps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.oro_mesh_set_texcoords.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _u32p]
     L.oro_mesh_texcoords.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _fp, _u32p]
+    L.oro_mesh_tangents.argtypes = [C.c_void_p, C.c_int, _fp, _fp]
     L.oro_mesh_set_motion.argtypes = [C.c_void_p, C.c_int, _fp]
     L.oro_scene_set_env_map.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.oro_scene_set_material_env_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
@@ -249,7 +250,11 @@ class OracleScene:
         self.L.oro_mesh_export(self.h, mesh, _p(v, _fp), _p(n, _fp), _p(vi, _u32p), _p(ni, _u32p))
         return v, n, vi, ni
 
-    def add_point_light(self, pos, power, cast_shadows=True):
+    def add_point_light(self, pos, power, cast_shadows=True, fast_shadows=True):
+        """fast_shadows False: Light::setFastShadows(false).  The point light's transparent-shadow
+        walk never traces (src/PointLight.cpp:49-70 loops while sampleHit.t < distance, from t =
+        distance), so such a light casts no shadow ray."""
+        cast_shadows = bool(cast_shadows) and bool(fast_shadows)
         l = Light()
         l.type = 0
         l.pos = _v3(pos)
@@ -309,6 +314,15 @@ class OracleScene:
         if n.value:
             self.L.oro_mesh_texcoords(self.h, mesh, C.byref(n), _p(uv, _fp), _p(ti, _u32p))
         return uv, ti
+
+    def tangents(self, mesh):
+        """(tangents, bitangents) per normal slot, (nn, 3) each; None without texture coordinates."""
+        nn = self.L.oro_mesh_tangents(self.h, mesh, None, None)
+        if nn <= 0:
+            return None
+        t, b = np.zeros((nn, 3), np.float32), np.zeros((nn, 3), np.float32)
+        self.L.oro_mesh_tangents(self.h, mesh, _p(t, _fp), _p(b, _fp))
+        return t, b
 
     def add_texture(self, rgb):
         a = np.ascontiguousarray(rgb, np.float32)

@@ -65,16 +65,17 @@ def materials_pair(P, O_, mat):
 
 
 def scene_pair(cfg, meshes=None, obj=None, floor=False, lights=None, num_paths=1, instances=None, subdivs=None,
-               extra=None, path_trace=None, moving=None):
+               extra=None, path_trace=None, moving=None, oracle=None):
     """Build (miro.Scene, OracleScene, camera dict) for a config dict.
     extra: [(mesh arrays, material dict), ...] added after the main geometry;
     moving: [(mesh arrays, time-1 vertices, material dict), ...] MBObject meshes
     (makeMBMeshObjs) added after those;
+    oracle: the scene that takes the oracle's calls (default: a new OracleScene);
     path_trace: (max_bounces, sample_env) turns Scene::m_pathTrace on."""
     lights = cfg["lights"] if lights is None else lights
     mat = cfg["material"]
     P = miro.Scene()
-    O_ = O.OracleScene()
+    O_ = O.OracleScene() if oracle is None else oracle
     all_mats = []   # (product, oracle id, description): per-material environment maps come last
 
     def materials_pair_(P, O_, m):
@@ -158,11 +159,9 @@ def scene_pair(cfg, meshes=None, obj=None, floor=False, lights=None, num_paths=1
             pl = miro.PointLight(); pl.setPosition(l["pos"]); pl.setPower(l["power"])
             fast = l.get("fast_shadows", True)
             pl.setFastShadows(fast)
+            pl.setCastShadows(l.get("cast_shadows", True))
             P.addLight(pl)
-            # Light::setFastShadows(false): the point light's transparent-shadow walk never
-            # traces (src/PointLight.cpp:49-70 loops while sampleHit.t < distance, from t =
-            # distance), so the oracle's light casts no shadow ray
-            O_.add_point_light(l["pos"], l["power"], cast_shadows=fast)
+            O_.add_point_light(l["pos"], l["power"], cast_shadows=l.get("cast_shadows", True), fast_shadows=fast)
         elif l["type"] == "dome":
             rgb = sky(l["sky"])
             l = dict(l, sky=rgb)
@@ -177,9 +176,10 @@ def scene_pair(cfg, meshes=None, obj=None, floor=False, lights=None, num_paths=1
             rl = miro.RectangleLight(); rl.setVertices(l["v1"], l["v2"], l["v3"]); rl.setPower(l["power"])
             rl.setSamples(l.get("samples", 1)); rl.setNoiseThreshold(l.get("noise", 0.001))
             rl.setFastShadows(l.get("fast_shadows", True))
+            rl.setCastShadows(l.get("cast_shadows", True))
             P.addLight(rl)
             O_.add_rect_light(l["v1"], l["v2"], l["v3"], l["power"], l.get("samples", 1), l.get("noise", 0.001),
-                              fast_shadows=l.get("fast_shadows", True))
+                              cast_shadows=l.get("cast_shadows", True), fast_shadows=l.get("fast_shadows", True))
     P.setBGColor(cfg["bg"])
     O_.set_bg(cfg["bg"])
     env = cfg.get("env")

@@ -1,6 +1,11 @@
 """Pins for the CPU oracle against measurements of the reference itself
 (explosion01.obj -> 11,647 QBVH nodes / 23,365 leaves),
-the loader facts and the committed golden fixtures."""
+the loader facts and the committed golden fixtures.
+
+These two counts were the only facts taken from the reference until tests/test_reference_cpu.py:
+that module compares the oracle with the reference's own code (loader arrays, hit records and
+per-ray traversal counts, frames), live where the reference can be compiled and from
+tests/golden/reference/ everywhere."""
 import json
 import os
 
