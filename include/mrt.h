@@ -421,6 +421,18 @@ int mrt_trace(mrt_scene* s, const float* o, const float* d, const float* tmin, c
 int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin,
                     const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream);
 
+/* Scene::trace (src/Scene.cpp:295-298) for rays with a time, Ray(o, d, time) (src/Ray.h:71):
+ * where an MBObject's triangle is (src/MBObject.cpp).  time: n floats, or NULL = mrt_trace
+ * exactly (the same kernel, the same bytes out).  With the rays of mrt_camera_rays, tmin =
+ * 0.001 and tmax = 1e12 (epsilon and MIRO_TMAX, src/Miro.h:35,56) the closest hits are the
+ * hit records of mrt_sample_rays, byte for byte.  Conventions of mrt_sample_rays: argument
+ * checks before any device call, n = 0 is MRT_OK, n at most 2^28, the async form takes device
+ * pointers, enqueues on `stream` and never synchronises. */
+int mrt_trace_rays(mrt_scene* s, const float* o, const float* d, const float* time, const float* tmin,
+                   const float* tmax, size_t n, int any_hit, mrt_hit* out);
+int mrt_trace_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
+                         const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream);
+
 /* ---- batched radiance query: Scene::sampleScene (src/Scene.cpp:219-243) for n caller
  * rays.  o, d: n*3 floats (d is used as given, as Ray(o, d) does: not normalised); time:
  * n floats or NULL (= 0, the Ray ctor default; the MBObject time of src/MBObject.cpp).
@@ -442,6 +454,48 @@ int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* t
 int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time,
                           size_t n, int32_t row_width, uint32_t seed, int32_t count_visits,
                           float* d_rgb, mrt_hit* d_hits, void* stream);
+/* ---- shade caller-supplied hits: the hit branch and the miss branch of Scene::sampleScene
+ * (src/Scene.cpp:224-241) -- m_numPaths Material::shade calls (src/Material.h:18) on the hit,
+ * the environment map or background of the ray's direction on a miss -- for n caller (ray,
+ * hit) pairs: mrt_sample_rays with its primary rays replaced by the caller's hit records.
+ * o, d, time, row_width, seed, count_visits, rgb as for mrt_sample_rays; ray i draws from
+ * the RNG stream of "pixel" i.  On the rays of mrt_camera_rays and the closest hits
+ * mrt_trace_rays(o, d, time, 0.001, 1e12) finds for them, rgb and the ray counts of
+ * mrt_scene_last_stats (shadow_rays, secondary_rays, primary_hits) equal those of
+ * mrt_sample_rays, bit for bit.
+ * Hit records: t, a, b and prim as mrt_trace / mrt_trace_rays (closest hit) / mrt_sample_rays
+ * / mrt_render write them; prim == -1 is a miss; inst is ignored (the id names the
+ * instance).  An any-hit result (any_hit = 1: prim = 1 is an occlusion flag, not an id) is
+ * NOT a hit record.  The records are not trusted.  Invalid: prim < -1, prim at or above the
+ * scene's hit-id count (the world objects plus every instance's BLAS objects), prim a
+ * ProxyObject's own world slot (which never hits), t, a or b not finite, |a| or |b| above
+ * 2^24.  The synchronous entry checks the host array before touching a device and returns
+ * MRT_ERR_INVALID, the first bad index in mrt_last_error.  The async entry checks on the
+ * device, before anything is indexed: an invalid record is shaded as a miss, and
+ * mrt_scene_last_stats then returns MRT_ERR_INVALID (the count in mrt_last_error), the way
+ * MRT_ERR_OVERFLOW is reported. */
+int mrt_shade_hits(mrt_scene* s, const float* o, const float* d, const float* time, const mrt_hit* hits, size_t n,
+                   int32_t row_width, uint32_t seed, int32_t count_visits, float* rgb);
+int mrt_shade_hits_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const mrt_hit* d_hits,
+                         size_t n, int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, void* stream);
+
+/* ---- the surface a hit names: Ray::getPoint (src/Ray.h) + HitInfo::getAllInfos
+ * (src/Ray.cpp:5-49), batched.  p = o + t * d; n / geo_n the interpolated and the geometric
+ * normal (through an instance's inverse transpose, src/Ray.cpp:27-31); (u, v) the
+ * interpolated texture coordinates with the tangent frame tan / bitan whenever the mesh has
+ * texture coordinates, else (u, v) = (a, b) and tan = bitan = 0; material the material id;
+ * mesh, tri, inst = HitInfo::obj / m_proxy as mrt_scene_prim_object gives them.  What
+ * Material::shade does to N afterwards (the Blinn flip, normal maps) is not applied.  Hit
+ * records and their validation as for mrt_shade_hits; a miss or an invalid record writes
+ * zeros and material = mesh = tri = inst = -1. */
+typedef struct {
+    float p[3], n[3], geo_n[3], tan[3], bitan[3], u, v;
+    int32_t material, mesh, tri, inst;
+} mrt_surface;
+int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n, mrt_surface* out);
+int mrt_hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
+                           mrt_surface* d_out, void* stream);
+
 /* Camera::eyeRayAdaptive(x, y, .5, .5, .5, .5) (src/Camera.cpp:116-174) for every pixel of
  * a width x height frame, on the host (no device is touched): the rays mrt_render traces
  * at 1 spp with this seed, index y*width + x, lens and getTimeSample time included.

@@ -144,6 +144,7 @@ struct StreamCtx {
     bool last_was_render = false;
     bool fused = false;                      // the last render ran frame1_kernel (one launch)
     bool chain_used = false;                 // the last render's shading ran the wavefront chain engine
+    bool supplied = false;                   // the last launch took the caller's hit records (CTR_INVALID is its count)
     uint16_t* bin_keys = nullptr;            // ray binning (mrt_bin.h): per-ray keys, two permutations
     uint32_t* bin_perm = nullptr;            //   [2][bin_cap] (0: shadow rays, 1: chain closest-hit entries)
     uint32_t* bin_hist = nullptr;            //   [2][kBinHist] bins + valid count
@@ -163,8 +164,15 @@ struct ShareBuf {
     hipEvent_t done = nullptr;   // the share's tiles are in the caller's gather buffer
 };
 
+// Runs of PrimShade records that are consecutive triangles of one mesh (world objects in
+// scene order, then every BLAS's): record start + k is triangle tri0 + k * step of `mesh`
+// (mrt_hit_surfaces: HitInfo::obj of a hit on the device).
+struct SurfaceGroup { int32_t start, mesh, tri0, step; };
+
 struct DeviceState {
     int device = -1;
+    SurfaceGroup* sgroups = nullptr;   // built by the first mrt_hit_surfaces call on this replica (one of bufs)
+    int n_sgroups = 0;
     QNode* nodes = nullptr;
     DLeaf* leaves = nullptr;
     PrimShade* prims = nullptr;

@@ -217,15 +217,15 @@ __global__ void __launch_bounds__(256) libm_kernel(int fn, const float* x, const
                : fn == 3 ? gl_sinf(x[i]) : fn == 4 ? gl_cosf(x[i]) : gl_powf(x[i], y[i]);
 }
 
-// Batched Scene::trace: one lane per query ray.
-template <bool ANY, bool INST = false>
-__global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DLeaf* leaves, const uint16_t* tables,
-                                                    int32_t* gstack, uint32_t gstride, const float* o, const float* d,
-                                                    const float* tmin, const float* tmax, size_t n, mrt_hit* out,
-                                                    unsigned long long* ctr, int fast_box,
-                                                    const DevInstance* insts, Trav alpha) {
-    __shared__ uint16_t s_tab[2048];
-    __shared__ int32_t s_stack[kLdsStack * kWG];
+// Batched Scene::trace: one lane per query ray.  TIMED: the rays carry a time
+// (mrt_trace_rays: Ray(o, d, time), where an MBObject lane's triangle is); without one
+// they are Ray(o, d), time 0 (src/Ray.h:71).
+template <bool ANY, bool INST, bool TIMED>
+__device__ __forceinline__ void trace_rays(uint16_t* s_tab, int32_t* s_stack, const QNode* nodes, const DLeaf* leaves,
+                                           const uint16_t* tables, int32_t* gstack, uint32_t gstride, const float* o,
+                                           const float* d, const float* time, const float* tmin, const float* tmax,
+                                           size_t n, mrt_hit* out, unsigned long long* ctr, int fast_box,
+                                           const DevInstance* insts, const Trav& alpha) {
     const int tid = threadIdx.x;
     for (int i = tid; i < 1024; i += kWG) reinterpret_cast<uint32_t*>(s_tab)[i] = reinterpret_cast<const uint32_t*>(tables)[i];
     __syncthreads();
@@ -234,10 +234,11 @@ __global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DL
     T.inst = insts;
     T.ovf = ctr + CTR_OVERFLOW;
     T.aprims = alpha.aprims; T.apuv = alpha.apuv; T.auv = alpha.auv; T.amats = alpha.amats; T.atex = alpha.atex;
-    T.pflags = alpha.pflags; T.verts = alpha.verts; T.verts2 = alpha.verts2;   // Ray time 0 (src/Ray.h:71)
+    T.pflags = alpha.pflags; T.verts = alpha.verts; T.verts2 = alpha.verts2;
     TravStats st;
     for (size_t i = (size_t)blockIdx.x * kWG + tid; i < n; i += (size_t)gridDim.x * kWG) {
         DRay r = make_ray(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
+        if constexpr (TIMED) r.time = time[i];
         DHit h{tmax[i], 0.f, 0.f, -1};
         bool hit = traverse<walk_opt(W_ANY, ANY) | walk_opt(W_INST, INST)>(T, r, tmin[i], h, st);
         mrt_hit res;
@@ -247,6 +248,29 @@ __global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DL
         out[i] = res;
     }
     if (st.overflow) atomicOr(&ctr[CTR_OVERFLOW], 1ull);
+}
+template <bool ANY, bool INST = false>
+__global__ void __launch_bounds__(kWG) trace_kernel(const QNode* nodes, const DLeaf* leaves, const uint16_t* tables,
+                                                    int32_t* gstack, uint32_t gstride, const float* o, const float* d,
+                                                    const float* tmin, const float* tmax, size_t n, mrt_hit* out,
+                                                    unsigned long long* ctr, int fast_box,
+                                                    const DevInstance* insts, Trav alpha) {
+    __shared__ uint16_t s_tab[2048];
+    __shared__ int32_t s_stack[kLdsStack * kWG];
+    trace_rays<ANY, INST, false>(s_tab, s_stack, nodes, leaves, tables, gstack, gstride, o, d, nullptr, tmin, tmax, n, out,
+                                 ctr, fast_box, insts, alpha);
+}
+// mrt_trace_rays with a time array: a kernel of its own, so trace_kernel keeps its code
+template <bool ANY, bool INST>
+__global__ void __launch_bounds__(kWG) trace_timed_kernel(const QNode* nodes, const DLeaf* leaves, const uint16_t* tables,
+                                                          int32_t* gstack, uint32_t gstride, const float* o, const float* d,
+                                                          const float* time, const float* tmin, const float* tmax, size_t n,
+                                                          mrt_hit* out, unsigned long long* ctr, int fast_box,
+                                                          const DevInstance* insts, Trav alpha) {
+    __shared__ uint16_t s_tab[2048];
+    __shared__ int32_t s_stack[kLdsStack * kWG];
+    trace_rays<ANY, INST, true>(s_tab, s_stack, nodes, leaves, tables, gstack, gstride, o, d, time, tmin, tmax, n, out, ctr,
+                                fast_box, insts, alpha);
 }
 
 // Device hit records (t, a, b, prim bits) -> mrt_hit (mrt_sample_rays_async): m_proxy from
@@ -269,6 +293,90 @@ __global__ void __launch_bounds__(256) hit_records_kernel(const float4* rec, siz
         }
         out[i] = h;
     }
+}
+
+// A caller's record as the kernels may use it: hit_record_class, and a ProxyObject's own
+// world slot (PrimShade::pad, set on upload) refused too.  prims is read only for an id the
+// comparisons have placed in [0, n_world).
+__device__ __forceinline__ bool hit_record_usable(const mrt_hit& h, int32_t n_world, int32_t n_ids, const PrimShade* prims,
+                                                  bool& invalid) {
+    int k = hit_record_class(h.t, h.a, h.b, h.prim, n_ids);
+    if (k > 0 && h.prim < n_world && prims[h.prim].pad != 0u) k = -1;
+    invalid = k < 0;
+    return k > 0;
+}
+
+// mrt_hit -> device hit records (t, a, b, prim bits) in the stream's hitbuf, in the place of
+// the primary launch (mrt_shade_hits): the inverse of hit_records_kernel.  A miss and an
+// invalid record become the walks' miss record; hits and invalid records are counted.
+__global__ void __launch_bounds__(256) hit_supply_kernel(const mrt_hit* in, size_t n, int32_t n_world, int32_t n_ids,
+                                                         const PrimShade* prims, float4* rec, unsigned long long* ctr) {
+    unsigned long long nh = 0, nbad = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const mrt_hit h = in[i];
+        bool bad;
+        const bool ok = hit_record_usable(h, n_world, n_ids, prims, bad);
+        rec[i] = ok ? make_float4(h.t, h.a, h.b, __int_as_float(h.prim)) : make_float4(1e12f, 0.f, 0.f, __int_as_float(-1));
+        nh += ok ? 1u : 0u;
+        nbad += bad ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        nh += __shfl_down(nh, off);
+        nbad += __shfl_down(nbad, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (nh) atomicAdd(&ctr[CTR_HITS], nh);
+        if (nbad) atomicAdd(&ctr[CTR_INVALID], nbad);
+    }
+}
+
+// Ray::getPoint + HitInfo::getAllInfos (src/Ray.cpp:5-49) per (ray, hit) pair: the shader's
+// own normals() and texcoords(), the frame always asked for.  No shading-side change of N.
+__global__ void __launch_bounds__(kWG) surface_kernel(RenderParams P, const float* o, const float* d, const mrt_hit* hits,
+                                                      size_t n, int32_t n_ids, const SurfaceGroup* groups, int32_t n_groups,
+                                                      mrt_surface* out) {
+    const uint16_t* rsqT = P.tables + 2048;
+    Trav T{};
+    TravStats st;
+    unsigned long long nbad = 0;
+    for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) {
+        const mrt_hit h = hits[i];
+        bool bad;
+        const bool ok = hit_record_usable(h, P.n_world, n_ids, P.prims, bad);
+        nbad += bad ? 1u : 0u;
+        mrt_surface s{};
+        s.material = s.mesh = s.tri = s.inst = -1;
+        if (ok) {
+            Shader<false, false, true> S{P, T, P.tables, rsqT, st, 0u, 0u, 0u, 0, 0u};
+            const DHit dh{h.t, h.a, h.b, h.prim};
+            v3 N, geoN, tn, bt;
+            uint32_t mat;
+            float u, v;
+            S.normals(dh, N, geoN, mat);
+            S.texcoords(dh, true, u, v, tn, bt);
+            int inst = -1;
+            if (h.prim >= P.n_world) S.inst_shade_index(h.prim, &inst);
+            int lo = 0, hi = n_groups - 1;   // the last run that starts at or before the record
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (groups[mid].start <= S.psi) lo = mid; else hi = mid - 1;
+            }
+            const SurfaceGroup g = groups[lo];
+            for (int k = 0; k < 3; k++) s.p[k] = o[3 * i + k] + h.t * d[3 * i + k];   // Ray::getPoint
+            s.n[0] = N.x; s.n[1] = N.y; s.n[2] = N.z;
+            s.geo_n[0] = geoN.x; s.geo_n[1] = geoN.y; s.geo_n[2] = geoN.z;
+            s.tan[0] = tn.x; s.tan[1] = tn.y; s.tan[2] = tn.z;
+            s.bitan[0] = bt.x; s.bitan[1] = bt.y; s.bitan[2] = bt.z;
+            s.u = u; s.v = v;
+            s.material = (int32_t)mat;
+            s.mesh = g.mesh;
+            s.tri = g.tri0 + (S.psi - g.start) * g.step;
+            s.inst = inst;
+        }
+        out[i] = s;
+    }
+    for (int off = 32; off > 0; off >>= 1) nbad += __shfl_down(nbad, off);
+    if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(&P.ctr[CTR_INVALID], nbad);
 }
 
 // Bucket tiles -> frames.  Item id = frame * buckets_per_frame + bucket; frame f
@@ -403,6 +511,36 @@ static void fill_params(const Scene& s, RenderParams& P) {
     P.sample_env = s.sample_env ? 1 : 0;
     P.mat_env = 0;
     for (const DevMaterial& m : s.materials) P.mat_env |= m.env >= 0 ? 1 : 0;
+}
+
+// The scene's hit ids (mrt_hit.prim of a hit) are [0, hit_id_count): the world objects, then
+// every instance's BLAS objects in instance order (build_qbvh sets hit_base that way).
+static int32_t hit_id_count(const Scene& s) {
+    int64_t n = (int64_t)s.obj_mesh.size();
+    if (!s.instances.empty()) {
+        const Instance& I = s.instances.back();
+        n = (int64_t)I.hit_base + (int64_t)s.blas[(size_t)I.blas].obj_mesh.size();
+    }
+    return (int32_t)std::min<int64_t>(n, INT32_MAX);
+}
+
+// The first record of a caller's host array that mrt_shade_hits / mrt_hit_surfaces refuse
+// (the device's test, hit_record_usable, on the host scene), or n: before any device call.
+static size_t first_bad_hit(const Scene& s, const mrt_hit* hits, size_t n, const char*& why) {
+    const int32_t n_ids = hit_id_count(s), n_world = (int32_t)s.obj_mesh.size();
+    for (size_t i = 0; i < n; i++) {
+        const mrt_hit& h = hits[i];
+        const int k = hit_record_class(h.t, h.a, h.b, h.prim, n_ids);
+        if (k < 0) {
+            why = (h.prim < -1 || h.prim >= n_ids) ? "prim outside the scene's hit ids" : "t, a or b not finite or out of range";
+            return i;
+        }
+        if (k > 0 && h.prim < n_world && !s.obj_inst.empty() && s.obj_inst[(size_t)h.prim] >= 0) {
+            why = "prim is a ProxyObject's own slot, which never hits";
+            return i;
+        }
+    }
+    return n;
 }
 
 // chain levels of the REC kernels: reflection / refraction bounces (< 5) plus
@@ -925,13 +1063,17 @@ static int launch_chain_adaptive(Scene& s, StreamCtx& c, RenderParams& P, bool c
 // Two launches on `stream`: primary rays -> hit records, then shading with
 // shadow rays.  Events bracket both (kernel_ms covers the whole frame).  With
 // adaptive supersampling (subdivs > 1) one fused launch (kernel 3) instead.
-static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hipStream_t stream, bool want_hits) {
+// supplied (ray mode only, mrt_shade_hits): the caller's hit records, one per ray -- the
+// primary launch is replaced by their conversion into the stream's hitbuf.
+static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hipStream_t stream, bool want_hits,
+                         const mrt_hit* supplied = nullptr) {
     DeviceState& d = *s.dev;
     StreamCtx* cp = nullptr;
     int rc = get_ctx(d, stream, cp);
     if (rc) return rc;
     StreamCtx& c = *cp;
     s.stats_final = false;
+    c.supplied = supplied != nullptr;
     if ((rc = ensure_slots(c, slots))) return rc;
     if (d.recursive) {
         P.lvl_words = level_words(s);
@@ -1009,9 +1151,17 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
     }
     const bool chk = d.has_alpha || d.has_mb;
     const bool rays = P.mode == 2;   // a ray batch: the kernels' ray-mode instantiations
-    if ((rc = launch(rays ? pick_primary_rays(count, fb, inst, chk, g_tune.walk_exit == 1)
-                          : pick_primary(g_tune.primary_waves, g_tune.primary_inst_waves, count, fb, inst, chk, g_tune.walk_exit == 1))))
+    if (supplied) {   // the caller's hits into hitbuf: no primary rays
+        const int g = (int)std::max<size_t>(1, std::min<size_t>((slots + 255) / 256, (size_t)d.cus * 8));
+        hipLaunchKernelGGL(hit_supply_kernel, dim3(g), dim3(256), 0, stream, supplied, slots, (int32_t)d.n_world,
+                           hit_id_count(s), d.prims, c.hitbuf, c.ctr);
+        HIP_OK(hipGetLastError());
+        which = 1;   // the wave log's primary record stays empty
+    } else if ((rc = launch(rays ? pick_primary_rays(count, fb, inst, chk, g_tune.walk_exit == 1)
+                                 : pick_primary(g_tune.primary_waves, g_tune.primary_inst_waves, count, fb, inst, chk,
+                                                g_tune.walk_exit == 1)))) {
         return rc;
+    }
     HIP_OK(hipEventRecord(c.evm, stream));
     P.queue = qbase + 8 * 32;
     const int max_sh = max_shadow_rays(s);
@@ -1522,11 +1672,12 @@ static int sample_rays_check(const mrt_scene* s, const float* o, const float* d,
     return MRT_OK;
 }
 
-int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
-                          int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, mrt_hit* d_hits,
-                          void* stream) {
-    int rc = sample_rays_check(s, d_o, d_d, n, row_width, d_rgb);
-    if (rc || n == 0) return rc;
+// the ray mode of the render dispatch on device arrays (checked by the caller, n > 0);
+// d_supplied: the caller's hit records in the primary launch's place (mrt_shade_hits)
+static int ray_batch_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
+                           int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, mrt_hit* d_hits,
+                           const mrt_hit* d_supplied, void* stream) {
+    int rc;
     Scene& S = s->impl;
     const int dev = S.dev ? S.dev->device : 0;
     if ((rc = ensure_device(S, dev))) return rc;
@@ -1546,7 +1697,7 @@ int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, cons
     P.tiles_x = w ? (int32_t)((w + 7) / 8) : 1;
     P.n_tiles = w ? (int32_t)((size_t)P.tiles_x * (((n + w - 1) / w + 7) / 8)) : (int32_t)((n + 63) / 64);
     P.out_rgb = d_rgb;
-    if ((rc = launch_render(S, P, n, count_visits != 0, (hipStream_t)stream, d_hits != nullptr))) return rc;
+    if ((rc = launch_render(S, P, n, count_visits != 0, (hipStream_t)stream, d_hits != nullptr, d_supplied))) return rc;
     S.last.primary_rays = (uint64_t)n;
     if (d_hits) {
         const DeviceState& d = *S.dev;
@@ -1556,6 +1707,175 @@ int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, cons
         HIP_OK(hipGetLastError());
     }
     return MRT_OK;
+}
+
+int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
+                          int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, mrt_hit* d_hits,
+                          void* stream) {
+    const int rc = sample_rays_check(s, d_o, d_d, n, row_width, d_rgb);
+    if (rc || n == 0) return rc;
+    return ray_batch_async(s, d_o, d_d, d_time, n, row_width, seed, count_visits, d_rgb, d_hits, nullptr, stream);
+}
+
+// ---- the hit / miss branch of Scene::sampleScene for caller (ray, hit) pairs (mrt_shade_hits)
+static int shade_hits_check(const mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n,
+                            int32_t row_width, const float* rgb) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (n && (!o || !d || !hits || !rgb)) { set_error("null ray / hit / output array"); return MRT_ERR_INVALID; }
+    if (row_width < 0) { set_error("row_width must be >= 0"); return MRT_ERR_INVALID; }
+    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    return MRT_OK;
+}
+// the synchronous entries refuse a bad record of the host array, naming the first
+static int host_hits_check(const mrt_scene* s, const mrt_hit* hits, size_t n) {
+    const char* why = "";
+    const size_t bad = first_bad_hit(s->impl, hits, n, why);
+    if (bad == n) return MRT_OK;
+    set_error("hit record " + std::to_string(bad) + ": " + why);
+    return MRT_ERR_INVALID;
+}
+
+int mrt_shade_hits_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const mrt_hit* d_hits,
+                         size_t n, int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, void* stream) {
+    const int rc = shade_hits_check(s, d_o, d_d, d_hits, n, row_width, d_rgb);
+    if (rc || n == 0) return rc;
+    return ray_batch_async(s, d_o, d_d, d_time, n, row_width, seed, count_visits, d_rgb, nullptr, d_hits, stream);
+}
+
+int mrt_shade_hits(mrt_scene* s, const float* o, const float* d, const float* time, const mrt_hit* hits, size_t n,
+                   int32_t row_width, uint32_t seed, int32_t count_visits, float* rgb) {
+    int rc = shade_hits_check(s, o, d, hits, n, row_width, rgb);
+    if (rc || n == 0) return rc;
+    if ((rc = host_hits_check(s, hits, n))) return rc;
+    Scene& S = s->impl;
+    const int dev = S.dev ? S.dev->device : 0;
+    if ((rc = ensure_device(S, dev))) return rc;
+    HIP_OK(hipSetDevice(dev));
+    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *brgb = nullptr;
+    mrt_hit* bh = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void**)&bo, n * 12));
+        HIP_OK(hipMalloc((void**)&bd, n * 12));
+        HIP_OK(hipMalloc((void**)&brgb, n * 12));
+        HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
+        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
+        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bh, hits, n * sizeof(mrt_hit), hipMemcpyHostToDevice));
+        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
+        int r = ray_batch_async(s, bo, bd, bt, n, row_width, seed, count_visits, brgb, nullptr, bh, nullptr);
+        if (r) return r;
+        HIP_OK(hipMemcpy(rgb, brgb, n * 12, hipMemcpyDeviceToHost));
+        mrt_stats tmp;
+        return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
+    };
+    rc = run();
+    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(brgb); (void)hipFree(bh);
+    return rc;
+}
+
+// ---- Ray::getPoint + HitInfo::getAllInfos for caller (ray, hit) pairs (mrt_hit_surfaces)
+static int hit_surfaces_check(const mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n,
+                              const mrt_surface* out) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (n && (!o || !d || !hits || !out)) { set_error("null ray / hit / output array"); return MRT_ERR_INVALID; }
+    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    return MRT_OK;
+}
+
+// the replica's SurfaceGroup table, built on first use
+static int surface_groups(const Scene& S, DeviceState& d) {
+    std::lock_guard<std::mutex> g(d.mu);
+    if (d.sgroups) return MRT_OK;
+    std::vector<SurfaceGroup> G;
+    int32_t at = 0;
+    auto runs = [&](const std::vector<int32_t>& mesh, const std::vector<int32_t>& tri) {
+        for (size_t i = 0; i < mesh.size(); i++, at++) {
+            bool extends = false;   // the run so far (of this array: i > 0) goes on with this record
+            if (i > 0 && G.back().mesh == mesh[i]) {
+                SurfaceGroup& b = G.back();
+                const int32_t k = at - b.start, step = tri[i] - tri[i - 1];
+                if (k == 1 && (step == 1 || step == -1)) {   // its second record sets the direction
+                    b.step = step;
+                    extends = true;
+                } else if (k > 1 && step == b.step) {
+                    extends = true;
+                }
+            }
+            if (!extends) G.push_back(SurfaceGroup{at, mesh[i], tri[i], 1});
+        }
+    };
+    runs(S.obj_mesh, S.obj_tri);
+    for (const Blas& b : S.blas) runs(b.obj_mesh, b.obj_tri);   // the PrimShade order of upload_scene
+    SurfaceGroup* p = nullptr;
+    HIP_OK(hipMalloc((void**)&p, std::max<size_t>(1, G.size()) * sizeof(SurfaceGroup)));
+    d.bufs.push_back(p);
+    if (!G.empty()) HIP_OK(hipMemcpy(p, G.data(), G.size() * sizeof(SurfaceGroup), hipMemcpyHostToDevice));
+    d.n_sgroups = (int)G.size();
+    d.sgroups = p;
+    return MRT_OK;
+}
+
+int mrt_hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
+                           mrt_surface* d_out, void* stream) {
+    int rc = hit_surfaces_check(s, d_o, d_d, d_hits, n, d_out);
+    if (rc || n == 0) return rc;
+    Scene& S = s->impl;
+    const int dev = S.dev ? S.dev->device : 0;
+    if ((rc = ensure_device(S, dev))) return rc;
+    HIP_OK(hipSetDevice(dev));
+    DeviceState& d = *S.dev;
+    if ((rc = surface_groups(S, d))) return rc;
+    StreamCtx* cp = nullptr;
+    if ((rc = get_ctx(d, (hipStream_t)stream, cp))) return rc;
+    StreamCtx& c = *cp;
+    S.stats_final = false;
+    HIP_OK(hipMemsetAsync(c.ctr, 0, kCtrBytes, (hipStream_t)stream));
+    c.last_was_render = false;
+    c.supplied = true;
+    RenderParams P{};
+    fill_params(S, P);
+    P.ctr = c.ctr;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)d.grid, (n + kWG - 1) / kWG));
+    HIP_OK(hipEventRecord(c.ev0, (hipStream_t)stream));
+    hipLaunchKernelGGL(surface_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, P, d_o, d_d, d_hits, n,
+                       hit_id_count(S), (const SurfaceGroup*)d.sgroups, (int32_t)d.n_sgroups, d_out);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c.ev1, (hipStream_t)stream));
+    d.last = &c;
+    S.last = mrt_stats{};
+    return MRT_OK;
+}
+
+int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n, mrt_surface* out) {
+    int rc = hit_surfaces_check(s, o, d, hits, n, out);
+    if (rc || n == 0) return rc;
+    if ((rc = host_hits_check(s, hits, n))) return rc;
+    Scene& S = s->impl;
+    const int dev = S.dev ? S.dev->device : 0;
+    if ((rc = ensure_device(S, dev))) return rc;
+    HIP_OK(hipSetDevice(dev));
+    float *bo = nullptr, *bd = nullptr;
+    mrt_hit* bh = nullptr;
+    mrt_surface* bs = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void**)&bo, n * 12));
+        HIP_OK(hipMalloc((void**)&bd, n * 12));
+        HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
+        HIP_OK(hipMalloc((void**)&bs, n * sizeof(mrt_surface)));
+        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bh, hits, n * sizeof(mrt_hit), hipMemcpyHostToDevice));
+        int r = mrt_hit_surfaces_async(s, bo, bd, bh, n, bs, nullptr);
+        if (r) return r;
+        HIP_OK(hipMemcpy(out, bs, n * sizeof(mrt_surface), hipMemcpyDeviceToHost));
+        return MRT_OK;
+    };
+    rc = run();
+    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bh); (void)hipFree(bs);
+    return rc;
 }
 
 int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* time, size_t n, int32_t row_width,
@@ -1635,6 +1955,8 @@ int mrt_scene_last_stats(const mrt_scene* cs, mrt_stats* out) {
     HIP_OK(hipEventSynchronize(x.ev1));
     unsigned long long c[CTR_N];
     HIP_OK(hipMemcpy(c, x.ctr, sizeof c, hipMemcpyDeviceToHost));
+    unsigned long long invalid = 0;   // a launch on the caller's hit records: those it refused
+    if (x.supplied) HIP_OK(hipMemcpy(&invalid, x.ctr + CTR_INVALID, sizeof invalid, hipMemcpyDeviceToHost));
     float ms = 0.f, ms1 = 0.f, ms2 = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, x.ev0, x.ev1));
     if (x.last_was_render) {
@@ -1676,12 +1998,16 @@ int mrt_scene_last_stats(const mrt_scene* cs, mrt_stats* out) {
     S.last.chain_fallbacks = (int32_t)c[CTR_FALLBACK];
     *out = S.last;
     if (c[CTR_OVERFLOW]) { set_error("traversal stack overflow"); return MRT_ERR_OVERFLOW; }
+    if (invalid) {
+        set_error(std::to_string(invalid) + " invalid hit record(s): treated as misses");
+        return MRT_ERR_INVALID;
+    }
     return MRT_OK;
 }
 
-int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin, const float* d_tmax, size_t n,
-                    int any_hit, mrt_hit* d_out, void* stream) {
-    if (!s || (n && (!d_o || !d_d || !d_tmin || !d_tmax || !d_out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+// mrt_trace_async / mrt_trace_rays_async: d_time == nullptr is Ray(o, d), trace_kernel
+static int trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
+                       const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream) {
     Scene& S = s->impl;
     int dev = S.dev ? S.dev->device : 0;
     int rc = ensure_device(S, dev);
@@ -1695,50 +2021,99 @@ int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const floa
     S.stats_final = false;
     HIP_OK(hipMemsetAsync(c.ctr, 0, CTR_N * sizeof(unsigned long long), (hipStream_t)stream));
     c.last_was_render = false;
+    c.supplied = false;
     int grid = (int)std::min<size_t>((size_t)d.grid, (n + kWG - 1) / kWG);
     HIP_OK(hipEventRecord(c.ev0, (hipStream_t)stream));
-    auto kern = any_hit ? (d.special ? trace_kernel<true, true> : trace_kernel<true, false>)
-                        : (d.special ? trace_kernel<false, true> : trace_kernel<false, false>);
     Trav alpha{};
     alpha.aprims = d.prims; alpha.apuv = d.puv; alpha.auv = d.uvs; alpha.amats = d.mats; alpha.atex = d.texs;
     alpha.pflags = d.pflags; alpha.verts = d.verts; alpha.verts2 = d.verts2;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, d.nodes, d.leaves, d.tables, c.gstack,
-                       d.gthreads, d_o, d_d, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
+    if (d_time) {
+        auto kern = any_hit ? (d.special ? trace_timed_kernel<true, true> : trace_timed_kernel<true, false>)
+                            : (d.special ? trace_timed_kernel<false, true> : trace_timed_kernel<false, false>);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, d.nodes, d.leaves, d.tables, c.gstack,
+                           d.gthreads, d_o, d_d, d_time, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
+    } else {
+        auto kern = any_hit ? (d.special ? trace_kernel<true, true> : trace_kernel<true, false>)
+                            : (d.special ? trace_kernel<false, true> : trace_kernel<false, false>);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, d.nodes, d.leaves, d.tables, c.gstack,
+                           d.gthreads, d_o, d_d, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
+    }
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(c.ev1, (hipStream_t)stream));
     d.last = &c;
     return MRT_OK;
 }
 
-int mrt_trace(mrt_scene* s, const float* o, const float* d, const float* tmin, const float* tmax, size_t n, int any_hit,
-              mrt_hit* out) {
-    if (!s || (n && (!o || !d || !tmin || !tmax || !out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin, const float* d_tmax, size_t n,
+                    int any_hit, mrt_hit* d_out, void* stream) {
+    if (!s || (n && (!d_o || !d_d || !d_tmin || !d_tmax || !d_out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    return trace_async(s, d_o, d_d, nullptr, d_tmin, d_tmax, n, any_hit, d_out, stream);
+}
+
+// ---- Scene::trace for rays with a time (mrt_trace_rays): the argument checks of both entries
+static int trace_rays_check(const mrt_scene* s, const float* o, const float* d, const float* tmin, const float* tmax,
+                            size_t n, const mrt_hit* out) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (n && (!o || !d || !tmin || !tmax || !out)) { set_error("null ray / bound / output array"); return MRT_ERR_INVALID; }
+    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    return MRT_OK;
+}
+
+int mrt_trace_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
+                         const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream) {
+    const int rc = trace_rays_check(s, d_o, d_d, d_tmin, d_tmax, n, d_out);
+    if (rc || n == 0) return rc;
+    return trace_async(s, d_o, d_d, d_time, d_tmin, d_tmax, n, any_hit, d_out, stream);
+}
+
+// mrt_trace / mrt_trace_rays: host arrays in and out (time nullable)
+static int trace_sync(mrt_scene* s, const float* o, const float* d, const float* time, const float* tmin,
+                      const float* tmax, size_t n, int any_hit, mrt_hit* out) {
     Scene& S = s->impl;
     int dev = S.dev ? S.dev->device : 0;
     int rc = ensure_device(S, dev);
     if (rc) return rc;
     if (n == 0) return MRT_OK;
     HIP_OK(hipSetDevice(dev));
-    float *bo = nullptr, *bd = nullptr, *bmin = nullptr, *bmax = nullptr;
+    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *bmin = nullptr, *bmax = nullptr;
     mrt_hit* bout = nullptr;
-    HIP_OK(hipMalloc((void**)&bo, n * 12));
-    HIP_OK(hipMalloc((void**)&bd, n * 12));
-    HIP_OK(hipMalloc((void**)&bmin, n * 4));
-    HIP_OK(hipMalloc((void**)&bmax, n * 4));
-    HIP_OK(hipMalloc((void**)&bout, n * sizeof(mrt_hit)));
-    HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bmin, tmin, n * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bmax, tmax, n * 4, hipMemcpyHostToDevice));
-    rc = mrt_trace_async(s, bo, bd, bmin, bmax, n, any_hit, bout, nullptr);
-    if (rc == MRT_OK) {
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void**)&bo, n * 12));
+        HIP_OK(hipMalloc((void**)&bd, n * 12));
+        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
+        HIP_OK(hipMalloc((void**)&bmin, n * 4));
+        HIP_OK(hipMalloc((void**)&bmax, n * 4));
+        HIP_OK(hipMalloc((void**)&bout, n * sizeof(mrt_hit)));
+        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
+        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bmin, tmin, n * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bmax, tmax, n * 4, hipMemcpyHostToDevice));
+        int r = trace_async(s, bo, bd, bt, bmin, bmax, n, any_hit, bout, nullptr);
+        if (r) return r;
         HIP_OK(hipMemcpy(out, bout, n * sizeof(mrt_hit), hipMemcpyDeviceToHost));
         unsigned long long c[CTR_N];
         HIP_OK(hipMemcpy(c, S.dev->last->ctr, sizeof c, hipMemcpyDeviceToHost));
-        if (c[CTR_OVERFLOW]) { set_error("traversal stack overflow"); rc = MRT_ERR_OVERFLOW; }
-    }
-    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bmin); (void)hipFree(bmax); (void)hipFree(bout);
+        if (c[CTR_OVERFLOW]) { set_error("traversal stack overflow"); return MRT_ERR_OVERFLOW; }
+        return MRT_OK;
+    };
+    rc = run();
+    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(bmin); (void)hipFree(bmax); (void)hipFree(bout);
     return rc;
+}
+
+int mrt_trace(mrt_scene* s, const float* o, const float* d, const float* tmin, const float* tmax, size_t n, int any_hit,
+              mrt_hit* out) {
+    if (!s || (n && (!o || !d || !tmin || !tmax || !out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    return trace_sync(s, o, d, nullptr, tmin, tmax, n, any_hit, out);
+}
+
+int mrt_trace_rays(mrt_scene* s, const float* o, const float* d, const float* time, const float* tmin, const float* tmax,
+                   size_t n, int any_hit, mrt_hit* out) {
+    const int rc = trace_rays_check(s, o, d, tmin, tmax, n, out);
+    if (rc || n == 0) return rc;
+    return trace_sync(s, o, d, time, tmin, tmax, n, any_hit, out);
 }
 
 int mrt_debug_wave_log(const mrt_scene* cs, int launch, uint64_t* out, int32_t max_waves) {

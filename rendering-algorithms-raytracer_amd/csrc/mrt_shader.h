@@ -36,6 +36,25 @@ static constexpr size_t kCtrBytes = (CTR_N * sizeof(unsigned long long) + 4 * 8 
 #else   // A/B build: round 3's unpadded length
 static constexpr size_t kCtrBytes = CTR_N * sizeof(unsigned long long) + 4 * 8 * 128;
 #endif
+// One more statistic, in the block's padding past the work counters (so CTR_N, the work
+// counters' place and every kernel that names them stay as they are): the caller's hit
+// records mrt_shade_hits / mrt_hit_surfaces refused (hit_record_class) and treated as misses
+static constexpr int CTR_INVALID = (CTR_N * (int)sizeof(unsigned long long) + 4 * 8 * 128) / (int)sizeof(unsigned long long);
+static_assert((size_t)(CTR_INVALID + 1) * sizeof(unsigned long long) <= kCtrBytes, "CTR_INVALID lies in the block's padding");
+// A caller's hit record (mrt_shade_hits / mrt_hit_surfaces), judged by comparisons alone,
+// before anything is indexed: 0 a miss (prim == -1), 1 a hit whose id lies in the scene's
+// hit-id range [0, n_ids) -- the caller then refuses a ProxyObject's own world slot -- and
+// -1 invalid: an id outside {-1} + [0, n_ids), t, a or b not finite, or a or b beyond
+// +-kHitBaryMax.  The walks' hits have a, b >= 0 and a + b <= 1 (tri_test); DESIGN.md §6b
+// has the argument that no index the shading forms from (a, b) leaves its array.
+static constexpr float kHitBaryMax = 16777216.0f;   // 2^24
+MRT_HD int hit_record_class(float t, float a, float b, int32_t prim, int32_t n_ids) {
+    if (prim == -1) return 0;
+    if (prim < 0 || prim >= n_ids) return -1;
+    // (x - x is 0 for a finite x and NaN otherwise; the range test also refuses NaN)
+    if (!(t - t == 0.0f) || !(a >= -kHitBaryMax && a <= kHitBaryMax) || !(b >= -kHitBaryMax && b <= kHitBaryMax)) return -1;
+    return 1;
+}
 // Shadow rays of the general shading path, wavefront style (ShadowMode): kernel
 // 2a runs the shading code and writes every shadow ray to its slot, kernel 2b
 // traces all of them any-hit (few registers, full occupancy), kernel 2c runs the
@@ -575,16 +594,16 @@ struct Shader {
     // last normals() call.  (u, v) interpolate the texture coordinates, or are
     // (a, b) without them; the tangent frame interpolates over the normal indices.
     int32_t psi = 0;   // PrimShade index of the last normals() call
-    __device__ void maps(const DHit& h, const DevMaterial& M, bool blinn, v3& N, v3& kd, float& spec_amt, float& refl,
-                         float& refr) {
-        float u = h.a, v = h.b;
-        v3 T = mk(0, 0, 0), BT = mk(0, 0, 0);
-        const bool nmap = blinn && M.maps[kMapNormal] >= 0;
+    // (u, v) and, with `frame`, the tangent frame: maps() asks for the frame when a normal map
+    // reads it, mrt_hit_surfaces always (getAllInfos computes it with the texture coordinates)
+    __device__ __forceinline__ void texcoords(const DHit& h, bool frame, float& u, float& v, v3& T, v3& BT) {
+        u = h.a; v = h.b;
+        T = mk(0, 0, 0); BT = mk(0, 0, 0);
         if (P.puv) {
             const uint4 t = P.puv[psi];
             if (t.w) {
                 const float c = 1.0f - h.a - h.b;
-                if (nmap) {
+                if (frame) {
                     const PrimShade ps = P.prims[psi];
                     const float4 t0 = P.tans[ps.n[0]], t1 = P.tans[ps.n[1]], t2 = P.tans[ps.n[2]];
                     const float4 b0 = P.btans[ps.n[0]], b1 = P.btans[ps.n[1]], b2 = P.btans[ps.n[2]];
@@ -598,6 +617,13 @@ struct Shader {
                 v = a0.y * c + a1.y * h.a + a2.y * h.b;
             }
         }
+    }
+    __device__ void maps(const DHit& h, const DevMaterial& M, bool blinn, v3& N, v3& kd, float& spec_amt, float& refl,
+                         float& refr) {
+        float u, v;
+        v3 T, BT;
+        const bool nmap = blinn && M.maps[kMapNormal] >= 0;
+        texcoords(h, nmap, u, v, T, BT);
         auto look = [&](int tex) {
             const DevTexture& X = P.texs[tex];
             return tex_lookup4(X.data, X.W, X.H, X.type, u, v);

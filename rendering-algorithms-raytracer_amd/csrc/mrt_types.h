@@ -50,7 +50,7 @@ struct alignas(16) PrimShade {
     uint32_t v[3];
     uint32_t mat;
     uint32_t n[3];
-    uint32_t pad;
+    uint32_t pad;   // 1: a ProxyObject's own world slot (no triangle; never a hit), else 0
 };
 static_assert(sizeof(PrimShade) == 32, "PrimShade is 32 B");
 

@@ -124,7 +124,10 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
     // PrimShade: the world objects (a ProxyObject's own slot stays zero), then each BLAS's objects
     auto shade_rec = [&](int32_t mesh, int32_t tri) {
         PrimShade p{};
-        if (mesh < 0) return p;
+        if (mesh < 0) {   // a ProxyObject's own world slot: never a hit (hit_record_usable refuses it by this mark)
+            p.pad = 1u;
+            return p;
+        }
         const Mesh& m = s.meshes[mesh];
         const size_t t = (size_t)tri;
         for (int k = 0; k < 3; k++) {

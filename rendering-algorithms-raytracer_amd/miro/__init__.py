@@ -408,6 +408,10 @@ class HitInfo:
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("a", "<f4"), ("b", "<f4"), ("prim", "<i4"), ("inst", "<i4")])
+# mrt_surface (Scene.hitSurfaces): Ray::getPoint + HitInfo::getAllInfos of a hit
+SURFACE_DTYPE = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("geo_n", "<f4", 3), ("tan", "<f4", 3), ("bitan", "<f4", 3),
+                          ("u", "<f4"), ("v", "<f4"), ("material", "<i4"), ("mesh", "<i4"), ("tri", "<i4"),
+                          ("inst", "<i4")])
 
 
 def makeMeshObjs(scene: "Scene", mesh: TriangleMesh, material):
@@ -800,6 +804,123 @@ class Scene:
                                 hits.ctypes.data if want_hits else None), "sampleRays")
         self.last_stats = self.stats()
         return (rgb, hits) if want_hits else rgb
+
+    # -- assemble sampleScene yourself: trace (with ray times), edit or filter the hits, shade them
+    def _pairs(self, what, o, d, time=None, hits=None):
+        """Shape checks shared by traceRays / shadeHits / hitSurfaces: (shape, n, tensors?)."""
+        shape = tuple(o.shape)
+        if len(shape) not in (2, 3) or shape[-1] != 3 or tuple(d.shape) != shape:
+            raise MRTError(f"{what}: o and d must both be (n, 3) or (H, W, 3)")
+        n = int(np.prod(shape[:-1]))
+        if time is not None and int(np.prod(tuple(time.shape))) != n:
+            raise MRTError(f"{what}: time must hold one value per ray")
+        tensors = hasattr(o, "data_ptr")
+        if tensors:
+            import torch
+            for x in [o, d] + ([time] if time is not None else []):
+                if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.device.index == self.device):
+                    raise MRTError(f"{what}: tensors must be contiguous float32 on the scene's device")
+        if hits is not None:
+            if tensors:
+                import torch
+                if not (hasattr(hits, "data_ptr") and hits.is_cuda and hits.dtype == torch.int32 and hits.is_contiguous()
+                        and tuple(hits.shape) == (n, 5) and hits.device.index == self.device):
+                    raise MRTError(f"{what}: hits must be a contiguous (n, 5) int32 tensor on the scene's device")
+            elif getattr(hits, "dtype", None) != HIT_DTYPE or int(np.prod(hits.shape)) != n:
+                raise MRTError(f"{what}: hits must be a HIT_DTYPE array with one record per ray")
+        return shape, n, tensors
+
+    def traceRays(self, o, d, time=None, tmin=0.001, tmax=1e12, any_hit=False):
+        """Scene::trace for rays with a time (mrt_trace_rays): o, d (n, 3) or (H, W, 3), time
+        (n,) / (H, W) or None (= traceBatch), tmin / tmax scalars or one per ray (defaults: the
+        reference's epsilon and MIRO_TMAX, the bounds of a camera ray).  numpy in: a HIT_DTYPE
+        array of the rays' shape; torch device tensors: mrt_trace_rays_async on the current
+        stream, an (n, 5) int32 tensor (t, a, b bits, prim, inst)."""
+        L = lib()
+        shape, n, tensors = self._pairs("traceRays", o, d, time)
+        check(L.mrt_scene_upload(self.handle, self.device), "upload")
+        if tensors:
+            import torch
+
+            def bound(x):
+                if hasattr(x, "data_ptr"):
+                    return x.to(device=o.device, dtype=torch.float32).reshape(-1).contiguous()
+                return torch.full((n,), float(x), dtype=torch.float32, device=o.device)
+            lo, hi = bound(tmin), bound(tmax)
+            if lo.numel() != n or hi.numel() != n:
+                raise MRTError("traceRays: tmin / tmax must be scalars or hold one value per ray")
+            out = torch.empty((n, 5), dtype=torch.int32, device=o.device)
+            stream = torch.cuda.current_stream(o.device).cuda_stream
+            check(L.mrt_trace_rays_async(self.handle, o.data_ptr(), d.data_ptr(),
+                                         time.data_ptr() if time is not None else None, lo.data_ptr(), hi.data_ptr(),
+                                         n, int(any_hit), out.data_ptr(), stream), "traceRays")
+            return out   # (lo / hi were made on this stream: the allocator frees them in its order)
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        t = np.ascontiguousarray(time, np.float32) if time is not None else None
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32).reshape(-1), (n,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32).reshape(-1), (n,)))
+        out = np.zeros(shape[:-1], HIT_DTYPE)
+        check(L.mrt_trace_rays(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None,
+                               lo.ctypes.data, hi.ctypes.data, n, int(any_hit), out.ctypes.data), "traceRays")
+        return out
+
+    def shadeHits(self, o, d, hits, time=None, seed=0, count_visits=False, row_width=None):
+        """The hit / miss branch of Scene::sampleScene for caller (ray, hit) pairs
+        (mrt_shade_hits): sampleRays with its primary rays replaced by `hits` -- closest-hit
+        records as traceRays / sampleRays(want_hits=True) give them (not any-hit results), prim
+        -1 = a miss.  numpy: a HIT_DTYPE array, checked on the host (MRTError names the first
+        bad record); torch: an (n, 5) int32 device tensor on the current stream, bad records
+        shaded as misses and reported by stats() as MRT_ERR_INVALID.  Returns rgb in the
+        rays' shape."""
+        L = lib()
+        shape, n, tensors = self._pairs("shadeHits", o, d, time, hits)
+        if row_width is None:
+            row_width = shape[1] if len(shape) == 3 else 0
+        check(L.mrt_scene_upload(self.handle, self.device), "upload")
+        if tensors:
+            import torch
+            rgb = torch.empty(shape, dtype=torch.float32, device=o.device)
+            stream = torch.cuda.current_stream(o.device).cuda_stream
+            check(L.mrt_shade_hits_async(self.handle, o.data_ptr(), d.data_ptr(),
+                                         time.data_ptr() if time is not None else None, hits.data_ptr(), n,
+                                         int(row_width), int(seed), int(count_visits), rgb.data_ptr(), stream),
+                  "shadeHits")
+            return rgb
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        t = np.ascontiguousarray(time, np.float32) if time is not None else None
+        h = np.ascontiguousarray(hits)
+        rgb = np.zeros(shape, np.float32)
+        check(L.mrt_shade_hits(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None,
+                               h.ctypes.data, n, int(row_width), int(seed), int(count_visits), rgb.ctypes.data),
+              "shadeHits")
+        self.last_stats = self.stats()
+        return rgb
+
+    def hitSurfaces(self, o, d, hits):
+        """Ray::getPoint + HitInfo::getAllInfos per (ray, hit) pair (mrt_hit_surfaces): a
+        SURFACE_DTYPE array of the rays' shape -- p, n, geo_n, tan, bitan, u, v, material,
+        mesh, tri, inst; zeros and -1 for a miss.  torch device tensors: the current stream,
+        an (n, 21) int32 tensor of the same words (floats as bits;
+        x.cpu().numpy().view(SURFACE_DTYPE) names them)."""
+        L = lib()
+        shape, n, tensors = self._pairs("hitSurfaces", o, d, None, hits)
+        check(L.mrt_scene_upload(self.handle, self.device), "upload")
+        if tensors:
+            import torch
+            out = torch.empty((n, 21), dtype=torch.int32, device=o.device)
+            stream = torch.cuda.current_stream(o.device).cuda_stream
+            check(L.mrt_hit_surfaces_async(self.handle, o.data_ptr(), d.data_ptr(), hits.data_ptr(), n, out.data_ptr(),
+                                           stream), "hitSurfaces")
+            return out
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        h = np.ascontiguousarray(hits)
+        out = np.zeros(shape[:-1], SURFACE_DTYPE)
+        check(L.mrt_hit_surfaces(self.handle, o.ctypes.data, d.ctypes.data, h.ctypes.data, n, out.ctypes.data),
+              "hitSurfaces")
+        return out
 
     def primObject(self, prim: int):
         """HitInfo::obj / m_proxy of a hit id: (mesh id, triangle index, instance or -1)."""

@@ -30,6 +30,8 @@ EXPORTS = [
     "mrt_scene_mesh_set_texcoords", "mrt_scene_mesh_texcoords", "mrt_scene_set_mesh_motion", "mrt_scene_walk_info",
     "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close", "mrt_get_tuning",
     "mrt_walk_arrays_fit", "mrt_sample_rays", "mrt_sample_rays_async", "mrt_camera_rays",
+    "mrt_trace_rays", "mrt_trace_rays_async", "mrt_shade_hits", "mrt_shade_hits_async", "mrt_hit_surfaces",
+    "mrt_hit_surfaces_async",
 ]
 
 
@@ -59,6 +61,12 @@ class mrt_mesh(C.Structure):
 
 class mrt_hit(C.Structure):
     _fields_ = [("t", C.c_float), ("a", C.c_float), ("b", C.c_float), ("prim", C.c_int32), ("inst", C.c_int32)]
+
+
+class mrt_surface(C.Structure):
+    _fields_ = [("p", C.c_float * 3), ("n", C.c_float * 3), ("geo_n", C.c_float * 3), ("tan", C.c_float * 3),
+                ("bitan", C.c_float * 3), ("u", C.c_float), ("v", C.c_float), ("material", C.c_int32),
+                ("mesh", C.c_int32), ("tri", C.c_int32), ("inst", C.c_int32)]
 
 
 class mrt_bvh_info(C.Structure):
@@ -195,6 +203,14 @@ def load():
                                             C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mrt_camera_rays.argtypes = [C.POINTER(mrt_camera), C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
+    if hasattr(L, "mrt_shade_hits"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        vp = C.c_void_p
+        L.mrt_trace_rays.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
+        L.mrt_trace_rays_async.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp, vp]
+        L.mrt_shade_hits.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_int32, C.c_uint32, C.c_int32, vp]
+        L.mrt_shade_hits_async.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_int32, C.c_uint32, C.c_int32, vp, vp]
+        L.mrt_hit_surfaces.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+        L.mrt_hit_surfaces_async.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
