@@ -346,6 +346,44 @@ int mrt_scene_bvh_import(mrt_scene* s, int32_t nodes, int32_t leaves, const floa
 /* Copy the scene to device `device` (done implicitly by render/trace). */
 int mrt_scene_upload(mrt_scene* s, int device);
 
+/* ---- geometry that moves between frames: refit (no reference counterpart: the
+ * reference rebuilds).  Replace the vertices (nv*3 floats, packed) and, when not NULL,
+ * the normals (nn*3) of world mesh `mesh`, same counts and topology, then refit the
+ * world hierarchy on every uploaded replica of the scene: the tree keeps its topology,
+ * the leaf triangles are recomputed from the vertices and every box from its children
+ * (std::min / std::max merges in lane and slot order, so the result is exact and stated
+ * bit for bit; DESIGN.md "Refit").  Tree quality degrades under large deformation; a
+ * rebuild (mrt_scene_build_bvh) remains the remedy.
+ * *refit_ms (nullable): device time of the refit kernels on the current device.
+ * Scope:
+ *  - world (non-instanced) meshes without mrt_scene_set_mesh_motion.  A mesh of a BLAS
+ *    or a motion-blurred mesh returns MRT_ERR_INVALID (a BLAS refit moves the instance
+ *    box and the world tree above it; an MBObject lane's box needs both vertex sets).
+ *    Scenes that hold instances or motion-blurred meshes beside the updated mesh are
+ *    fine: their leaf lanes keep the box the build gave them.
+ *  - a scene whose hierarchy came from mrt_scene_bvh_import (it may share nodes between
+ *    parents) returns MRT_ERR_INVALID; an unbuilt scene MRT_ERR_NOT_BUILT.
+ *  - arguments are checked before any device call; every vertex and normal must be
+ *    finite, else MRT_ERR_INVALID with the first bad index in mrt_last_error.
+ *  - a scene that is built but not uploaded (or due for a re-upload) is refitted on the
+ *    host: the same arithmetic.
+ *  - a mesh with texture coordinates gets its tangent frames recomputed on the host
+ *    (TriangleMesh::preCalc) and uploaded.
+ * After an update of an uploaded scene mrt_scene_bvh_export returns the arrays the
+ * device holds, read back and converted to the canonical layout. */
+int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts,
+                          const float* normals, float* refit_ms);
+/* The same with device pointers, enqueued on `stream`, never synchronising (the first
+ * refit of a replica allocates and uploads its schedule).  Acts on the scene's current
+ * device; the vertices never visit the host, and are not checked: they must be finite.
+ * It needs the scene uploaded to exactly one device (else MRT_ERR_INVALID) and refuses
+ * a mesh with texture coordinates (its tangent accumulation is order-dependent and
+ * stays on the host).  The host copy is left stale: mrt_scene_bvh_export,
+ * mrt_scene_mesh_export, a re-upload after a scene change and an upload to a second
+ * device first read the device state back, synchronising. */
+int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts,
+                                const float* d_normals, void* stream);
+
 /* ---- frame entry: Scene::raytraceImage(Camera*, Image*) (src/Scene.cpp:85-217).
  * Synchronous, host buffers: rgb (W*H*3 floats, before Map) and rgb8 (W*H*3,
  * after Image::Map; nullable); hits (W*H, nullable).  1 spp primary + shadow. */

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <cmath>
 #include <new>
 #include <string>
 #include <vector>
@@ -64,6 +65,43 @@ static const TuneRow* tune_row(const char* key) {
         if (strcmp(r.key, key) == 0) return &r;
     set_error(std::string("unknown tuning key ") + key);
     return nullptr;
+}
+
+// mrt_scene_update_mesh / _async (mrt_refit.hip): which scenes and meshes a refit takes
+int refit_check(const Scene& S, int mesh, const float* verts, const float* normals) {
+    if (!S.built) { set_error("update_mesh: scene not built"); return MRT_ERR_NOT_BUILT; }
+    if (mesh < 0 || mesh >= (int)S.meshes.size()) { set_error("update_mesh: bad mesh id"); return MRT_ERR_INVALID; }
+    const Mesh& m = S.meshes[(size_t)mesh];
+    if (S.mesh_blas[(size_t)mesh] >= 0) {
+        set_error("update_mesh: the mesh belongs to a BLAS (an instanced mesh is not refitted: its instance boxes would move)");
+        return MRT_ERR_INVALID;
+    }
+    if (!m.verts2.empty()) {
+        set_error("update_mesh: the mesh has motion vertices (mrt_scene_set_mesh_motion): an MBObject's box needs both sets");
+        return MRT_ERR_INVALID;
+    }
+    if (S.imported) {
+        set_error("update_mesh: the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
+        return MRT_ERR_INVALID;
+    }
+    auto finite = [&](const float* p, size_t n, const char* what) {
+        for (size_t i = 0; i < 3 * n; i++)
+            if (!std::isfinite(p[i])) {
+                set_error(std::string("update_mesh: ") + what + " " + std::to_string(i / 3) + " is not finite");
+                return false;
+            }
+        return true;
+    };
+    if (verts && !finite(verts, m.verts.size(), "vertex")) return MRT_ERR_INVALID;
+    if (normals && !finite(normals, m.normals.size(), "normal")) return MRT_ERR_INVALID;
+    return MRT_OK;
+}
+
+void refit_set_mesh(Mesh& m, const float* verts, const float* normals) {
+    for (size_t i = 0; i < m.verts.size(); i++) m.verts[i] = mk(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]);
+    if (normals)
+        for (size_t i = 0; i < m.normals.size(); i++) m.normals[i] = mk(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+    mesh_tangents(m);   // TriangleMesh::preCalc of a texture-mapped mesh
 }
 
 }  // namespace mrt
@@ -389,6 +427,7 @@ int mrt_scene_mesh_info(const mrt_scene* s, int mesh, int32_t* nv, int32_t* nn, 
 
 int mrt_scene_mesh_export(const mrt_scene* s, int mesh, float* verts, float* normals, uint32_t* vidx, uint32_t* nidx) {
     if (!s || mesh < 0 || mesh >= (int)s->impl.meshes.size()) { set_error("bad mesh id"); return MRT_ERR_INVALID; }
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;   // vertices an async update left on the device
     const Mesh& m = s->impl.meshes[mesh];
     for (size_t i = 0; i < m.verts.size(); i++) { verts[3*i] = m.verts[i].x; verts[3*i+1] = m.verts[i].y; verts[3*i+2] = m.verts[i].z; }
     for (size_t i = 0; i < m.normals.size(); i++) { normals[3*i] = m.normals[i].x; normals[3*i+1] = m.normals[i].y; normals[3*i+2] = m.normals[i].z; }
@@ -558,6 +597,7 @@ int mrt_scene_build_bvh(mrt_scene* s) {
     if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
     for (auto& m : s->impl.meshes)
         if (m.material < 0 || m.material >= (int)s->impl.materials.size()) { set_error("mesh references unknown material"); return MRT_ERR_INVALID; }
+    if (const int rc = sync_host(s->impl)) return rc;   // the build reads the host vertices
     std::string err;
     int rc = build_qbvh(s->impl, err);
     if (rc != MRT_OK) set_error(err);
@@ -574,6 +614,8 @@ int mrt_scene_bvh_info(const mrt_scene* s, mrt_bvh_info* info) {
 int mrt_scene_bvh_export(const mrt_scene* s, float* node_boxes, int32_t* node_child, float* leaf_tris, int32_t* leaf_prims) {
     if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
     if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    // after a device refit: the arrays the device holds, read back and converted
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
     for (size_t i = 0; i < s->impl.nodes.size(); i++) {
         memcpy(node_boxes + 24 * i, s->impl.nodes[i].box, 96);
         memcpy(node_child + 4 * i, s->impl.nodes[i].child, 16);
@@ -590,6 +632,7 @@ int mrt_scene_bvh_import(mrt_scene* s, int32_t nodes, int32_t leaves, const floa
     if (!s || nodes < 1 || leaves < 0) { set_error("bad argument"); return MRT_ERR_INVALID; }
     Scene& S = s->impl;
     if (!S.built) { set_error("build the scene first (prim ids come from it)"); return MRT_ERR_NOT_BUILT; }
+    if (const int rc = sync_host(S)) return rc;
     std::vector<QNode> N((size_t)nodes);
     std::vector<QLeaf> L((size_t)leaves);
     for (int i = 0; i < nodes; i++) {
@@ -612,6 +655,7 @@ int mrt_scene_bvh_import(mrt_scene* s, int32_t nodes, int32_t leaves, const floa
     S.leaves.swap(L);
     S.info.nodes = nodes;
     S.info.leaves = leaves;
+    S.imported = true;
     S.dev_dirty = true;
     return MRT_OK;
 }

@@ -1167,6 +1167,7 @@ int build_qbvh(Scene& s, std::string& err) {
     s.info.max_depth = b.q_depth;
     s.info.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     s.built = true;
+    s.imported = false;
     s.dev_dirty = true;
     return MRT_OK;
 }
@@ -1235,6 +1236,79 @@ int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err) {
     s.built = false;
     s.dev_dirty = true;
     return (int)s.instances.size() - 1;
+}
+
+// ------------------------------------------------------------------ refit
+namespace {
+inline Box verts_box3(v3 A, v3 B, v3 C) {   // Builder::box3
+    return Box{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
+               {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
+}
+inline Box slot_box(const QNode& q, int k) {
+    return Box{{q.box[0 + k], q.box[4 + k], q.box[8 + k]}, {q.box[12 + k], q.box[16 + k], q.box[20 + k]}};
+}
+}  // namespace
+
+bool fixed_lane_box(const Scene& s, int32_t o, float box[6]) {
+    if (o < 0 || (size_t)o >= s.obj_mesh.size()) return false;
+    if (s.obj_inst[(size_t)o] >= 0) {   // ProxyObject::getAABB
+        memcpy(box, s.instances[(size_t)s.obj_inst[(size_t)o]].box, 6 * sizeof(float));
+        return true;
+    }
+    const Mesh& m = s.meshes[(size_t)s.obj_mesh[(size_t)o]];
+    if (m.verts2.empty()) return false;
+    const uint32_t* f = &m.vidx[3 * (size_t)s.obj_tri[(size_t)o]];   // MBObject::getAABB
+    const Box b = merge(verts_box3(m.verts[f[0]], m.verts[f[1]], m.verts[f[2]]),
+                        verts_box3(m.verts2[f[0]], m.verts2[f[1]], m.verts2[f[2]]));
+    for (int k = 0; k < 3; k++) { box[k] = b.mn[k]; box[3 + k] = b.mx[k]; }
+    return true;
+}
+
+// Same topology, new vertices.  A packet's box merges its lanes in lane order from
+// empty_box(), as build_bin does for a binary leaf; a slot that is an inner node takes the
+// merge of that child's used slots in slot order; empty slots keep their zero box.  Every
+// child of a built hierarchy has a larger number than its parent (qbuild), so one pass from
+// the last node to the first is bottom-up.
+void refit_host(Scene& s) {
+    std::vector<Box> lbox(s.leaves.size());
+    for (size_t li = 0; li < s.leaves.size(); li++) {
+        QLeaf& L = s.leaves[li];
+        Box b = empty_box();
+        for (int i = 0; i < 4; i++) {
+            const int32_t o = L.prim[i];
+            if (o < 0) continue;
+            float fb[6];
+            if (fixed_lane_box(s, o, fb)) {   // checkOut lanes: no triangle data, the build's box
+                b = merge(b, Box{{fb[0], fb[1], fb[2]}, {fb[3], fb[4], fb[5]}});
+                continue;
+            }
+            const Mesh& m = s.meshes[(size_t)s.obj_mesh[(size_t)o]];
+            const uint32_t* f = &m.vidx[3 * (size_t)s.obj_tri[(size_t)o]];
+            const v3 A = m.verts[f[0]], B = m.verts[f[1]], C = m.verts[f[2]];
+            L.t[0 + i] = A.x; L.t[4 + i] = A.y; L.t[8 + i] = A.z;
+            L.t[12 + i] = B.x - A.x; L.t[16 + i] = B.y - A.y; L.t[20 + i] = B.z - A.z;
+            L.t[24 + i] = C.x - A.x; L.t[28 + i] = C.y - A.y; L.t[32 + i] = C.z - A.z;
+            b = merge(b, verts_box3(A, B, C));
+        }
+        lbox[li] = b;
+    }
+    for (size_t qi = s.nodes.size(); qi-- > 0;) {
+        QNode& q = s.nodes[qi];
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = q.child[k];
+            if (c == kEmptySlot) continue;
+            Box b;
+            if (c < 0) b = lbox[(size_t)~c];
+            else {
+                const QNode& ch = s.nodes[(size_t)c];
+                b = empty_box();
+                for (int j = 0; j < 4; j++)
+                    if (ch.child[j] != kEmptySlot) b = merge(b, slot_box(ch, j));
+            }
+            q.box[0 + k] = b.mn[0]; q.box[4 + k] = b.mn[1]; q.box[8 + k] = b.mn[2];
+            q.box[12 + k] = b.mx[0]; q.box[16 + k] = b.mx[1]; q.box[20 + k] = b.mx[2];
+        }
+    }
 }
 
 }  // namespace mrt

@@ -212,6 +212,21 @@ struct DeviceState {
     bool lds_ok = false;         // the world hierarchy has kLdsNodes nodes for the LDS top-node walk (renumbered)
     std::atomic<int> lds_pick{-1};   // the last one-light frame ran the LDS top-node walk: 1 yes, 0 no, -1 none yet
     float bb_lo[3] = {0, 0, 0}, bb_hi[3] = {0, 0, 0};   // world root box (ray-binning origin cells)
+    // refit (mrt_refit.hip): per mesh the first float4 of its slice of verts / normals, the
+    // world hierarchy's size and its canonical -> device node numbers (the LDS breadth-first
+    // permutation; empty = identity); the rest is made by the first refit on this replica
+    std::vector<uint32_t> vbase, nbase;
+    std::vector<int32_t> node_perm;
+    uint32_t n_world_nodes = 0, n_world_leaves = 0;
+    bool refit_ready = false;
+    int32_t* refit_order = nullptr;       // world device node numbers sorted by height (one of bufs)
+    std::vector<uint32_t> refit_off;      //   height h holds refit_order[refit_off[h] .. refit_off[h + 1])
+    float4* refit_lbox = nullptr;         // per world packet: box min xyz, max xyz (2 float4; one of bufs)
+    float4* refit_fixed = nullptr;        // ProxyObject lanes' boxes by instance, then MBObject lanes' (2 float4 each)
+    int32_t* refit_mbslot = nullptr;      //   per world prim: its MBObject box after the instances', -1 = none
+    float* refit_stage = nullptr;         // the synchronous entry's packed vertices / normals on the device
+    size_t refit_stage_cap = 0;           //   floats
+    hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
     int cus = 0;
     bool point_only = false;
     bool dome = false;           // a dome light (incoherent shadow rays)
@@ -237,6 +252,7 @@ struct DeviceState {
 void free_replicas(Scene& s);
 int get_ctx(DeviceState& d, hipStream_t stream, StreamCtx*& out);   // scratch context of `stream`
 int ensure_device(Scene& s, int device);                            // the scene's replica on `device` becomes s.dev
+void root_box(const QNode& root, float lo[3], float hi[3]);         // union of the root's used slot boxes (finite values)
 
 }  // namespace mrt
 #endif   // __HIPCC__

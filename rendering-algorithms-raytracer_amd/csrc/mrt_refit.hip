@@ -1,0 +1,350 @@
+// mrt_refit.hip -- mrt_scene_update_mesh: new vertices for a world mesh, same topology, and
+// the world hierarchy refitted on the device: a scatter of the vertices into the mesh's
+// slice, one leaf kernel (triangles A, B-A, C-A and one box per packet) and one node kernel
+// launch per height, deepest first.  Every box is a min / max merge in a fixed order
+// (mrt_math.h std_min / std_max, as Builder::tri_aabb and merge): the result is stated bit
+// for bit by refit_host (host_build.cpp) and by tests/test_refit.py's numpy restatement.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "mrt_device.h"
+#include "mrt_kernels.h"
+
+namespace mrt {
+
+namespace {
+
+constexpr int kRefitWG = 256;
+
+struct DBox {
+    float lo[3], hi[3];
+};
+__device__ __forceinline__ DBox d_empty_box() {   // empty_box(): +-MIRO_TMAX
+    return DBox{{1e12f, 1e12f, 1e12f}, {-1e12f, -1e12f, -1e12f}};
+}
+__device__ __forceinline__ DBox d_merge(const DBox& a, const DBox& b) {
+    DBox r;
+    for (int k = 0; k < 3; k++) {
+        r.lo[k] = std_min(a.lo[k], b.lo[k]);
+        r.hi[k] = std_max(a.hi[k], b.hi[k]);
+    }
+    return r;
+}
+
+// n packed (x, y, z) -> float4 (x, y, z, w) at dst (and dst2: the time-1 copy of a static mesh)
+__global__ __launch_bounds__(kRefitWG) void refit_scatter_kernel(float4* __restrict__ dst, float4* __restrict__ dst2,
+                                                                 const float* __restrict__ src, uint32_t n, float w) {
+    const uint32_t i = blockIdx.x * kRefitWG + threadIdx.x;
+    if (i >= n) return;
+    const float* p = src + (size_t)i * 3;
+    const float4 v = make_float4(p[0], p[1], p[2], w);
+    dst[i] = v;
+    if (dst2) dst2[i] = v;
+}
+
+// One lane per packet lane of the world DLeaf range (n_lanes = 4 x packets, so the four
+// lanes of a packet are in one wave and all inside or all outside the range).
+__global__ __launch_bounds__(kRefitWG) void refit_leaf_kernel(DLeaf* __restrict__ leaves, uint32_t n_lanes,
+                                                              const PrimShade* __restrict__ prims,
+                                                              const float4* __restrict__ verts,
+                                                              const uint8_t* __restrict__ pflags,
+                                                              const int32_t* __restrict__ mbslot,
+                                                              const float4* __restrict__ fixed, int n_insts,
+                                                              float4* __restrict__ lbox) {
+    const uint32_t g = blockIdx.x * kRefitWG + threadIdx.x;
+    const bool in = g < n_lanes;
+    const uint32_t leaf = g >> 2, k = g & 3u;
+    DBox b = d_empty_box();
+    int used = 0;
+    if (in) {
+        const int32_t prim = leaves[leaf].prim[k];
+        int fx = -1;   // a ProxyObject / MBObject lane: its box of the build
+        if (prim <= -2) fx = -2 - prim;
+        else if (prim >= 0 && pflags && (pflags[prim] & 1u)) fx = n_insts + mbslot[prim];
+        if (fx >= 0) {
+            const float4 lo = fixed[2 * fx], hi = fixed[2 * fx + 1];
+            b = DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+            used = 1;
+        } else if (prim >= 0) {
+            const PrimShade ps = prims[prim];
+            const float4 A = verts[ps.v[0]], B = verts[ps.v[1]], C = verts[ps.v[2]];
+            float* t = leaves[leaf].tri[k];   // make_leaf: A, B - A, C - A
+            t[0] = A.x; t[1] = A.y; t[2] = A.z;
+            t[3] = B.x - A.x; t[4] = B.y - A.y; t[5] = B.z - A.z;
+            t[6] = C.x - A.x; t[7] = C.y - A.y; t[8] = C.z - A.z;
+            b = DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
+                     {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
+            used = 1;
+        }
+    }
+    // the packet's box: its used lanes merged in lane order from the empty box
+    DBox acc = d_empty_box();
+    for (int j = 0; j < 4; j++) {
+        DBox o;
+        for (int a = 0; a < 3; a++) {
+            o.lo[a] = __shfl(b.lo[a], j, 4);
+            o.hi[a] = __shfl(b.hi[a], j, 4);
+        }
+        if (__shfl(used, j, 4)) acc = d_merge(acc, o);
+    }
+    if (in && k == 0) {
+        lbox[2 * (size_t)leaf] = make_float4(acc.lo[0], acc.lo[1], acc.lo[2], 0.f);
+        lbox[2 * (size_t)leaf + 1] = make_float4(acc.hi[0], acc.hi[1], acc.hi[2], 0.f);
+    }
+}
+
+// One lane per slot of the n nodes of one height (order[0 .. n)): a leaf slot takes its
+// packet's box, an inner slot the merge of that child's used slots in slot order (the
+// child is of a smaller height: an earlier launch wrote it).  Empty slots, the child words
+// and the slot kinds are not touched.
+__global__ __launch_bounds__(kRefitWG) void refit_node_kernel(QNode* __restrict__ nodes,
+                                                              const int32_t* __restrict__ order, uint32_t n,
+                                                              const float4* __restrict__ lbox) {
+    const uint32_t g = blockIdx.x * kRefitWG + threadIdx.x;
+    if (g >= 4u * n) return;
+    const uint32_t k = g & 3u;
+    QNode* q = nodes + order[g >> 2];
+    const int32_t c = q->child[k];
+    if (c == kEmptySlot) return;
+    DBox b;
+    if (c < 0) {
+        const size_t leaf = (size_t)(~(uint32_t)c >> 4);   // leaf_child
+        const float4 lo = lbox[2 * leaf], hi = lbox[2 * leaf + 1];
+        b = DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+    } else {
+        const QNode* ch = nodes + c;
+        b = d_empty_box();
+        for (int j = 0; j < 4; j++) {
+            if (ch->child[j] == kEmptySlot) continue;
+            const DBox o{{ch->box[0 + j], ch->box[4 + j], ch->box[8 + j]}, {ch->box[12 + j], ch->box[16 + j], ch->box[20 + j]}};
+            b = d_merge(b, o);
+        }
+    }
+    q->box[0 + k] = b.lo[0]; q->box[4 + k] = b.lo[1]; q->box[8 + k] = b.lo[2];
+    q->box[12 + k] = b.hi[0]; q->box[16 + k] = b.hi[1]; q->box[20 + k] = b.hi[2];
+}
+
+template <typename T>
+int dev_array(DeviceState& d, T*& dst, const void* src, size_t bytes) {
+    HIP_OK(hipMalloc((void**)&dst, bytes ? bytes : 16));
+    d.bufs.push_back(dst);   // freed with the replica
+    if (bytes) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return MRT_OK;
+}
+
+// What the refit of replica d needs beyond the upload, made once (the topology never
+// changes while the replica lives): the node lists by height in device numbers, the packet
+// box scratch and the fixed boxes of ProxyObject / MBObject lanes.  The current device is d's.
+int prepare(const Scene& s, DeviceState& d) {
+    if (d.refit_ready) return MRT_OK;
+    const size_t nw = s.nodes.size();
+    if (nw != d.n_world_nodes || s.leaves.size() != d.n_world_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    // heights: every child has a larger canonical number than its parent (qbuild)
+    std::vector<int32_t> height(nw, 0);
+    int32_t top = 0;
+    for (size_t i = nw; i-- > 0;) {
+        int32_t h = 0;
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = s.nodes[i].child[k];
+            if (c < 0) continue;
+            if ((size_t)c <= i || (size_t)c >= nw) { set_error("refit: the hierarchy is not a tree in build order"); return MRT_ERR_INVALID; }
+            h = std::max(h, height[(size_t)c] + 1);
+        }
+        height[i] = h;
+        top = std::max(top, h);
+    }
+    d.refit_off.assign((size_t)top + 2, 0);
+    for (size_t i = 0; i < nw; i++) d.refit_off[(size_t)height[i] + 1]++;
+    for (size_t h = 0; h + 1 < d.refit_off.size(); h++) d.refit_off[h + 1] += d.refit_off[h];
+    std::vector<int32_t> order(nw);
+    std::vector<uint32_t> at(d.refit_off.begin(), d.refit_off.end() - 1);
+    for (size_t i = 0; i < nw; i++) order[at[(size_t)height[i]]++] = d.node_perm.empty() ? (int32_t)i : d.node_perm[i];
+    // fixed boxes: instance i at i, then the MBObject lanes
+    std::vector<float4> fixed(2 * s.instances.size());
+    for (size_t i = 0; i < s.instances.size(); i++) {
+        const float* b = s.instances[i].box;
+        fixed[2 * i] = make_float4(b[0], b[1], b[2], 0.f);
+        fixed[2 * i + 1] = make_float4(b[3], b[4], b[5], 0.f);
+    }
+    std::vector<int32_t> mbslot;
+    if (d.has_mb) {
+        mbslot.assign(s.obj_mesh.size(), -1);
+        int32_t next = 0;
+        for (size_t o = 0; o < s.obj_mesh.size(); o++) {
+            float b[6];
+            if (s.obj_inst[o] >= 0 || !fixed_lane_box(s, (int32_t)o, b)) continue;
+            mbslot[o] = next++;
+            fixed.push_back(make_float4(b[0], b[1], b[2], 0.f));
+            fixed.push_back(make_float4(b[3], b[4], b[5], 0.f));
+        }
+    }
+    int rc;
+    if ((rc = dev_array(d, d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_array(d, d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4)))) return rc;
+    if ((rc = dev_array(d, d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t)))) return rc;
+    HIP_OK(hipMalloc((void**)&d.refit_lbox, std::max<size_t>(1, s.leaves.size()) * 2 * sizeof(float4)));
+    d.bufs.push_back(d.refit_lbox);
+    HIP_OK(hipEventCreate(&d.refit_ev0));
+    HIP_OK(hipEventCreate(&d.refit_ev1));
+    d.refit_ready = true;
+    return MRT_OK;
+}
+
+inline dim3 blocks(size_t n) { return dim3((unsigned)((n + kRefitWG - 1) / kRefitWG)); }
+
+// Enqueue on `stream`: scatter nv vertices (and nn normals) from packed device arrays into
+// mesh m's slices, then the leaf kernel and the node kernels.
+int enqueue(DeviceState& d, int m, const float* d_verts, uint32_t nv, const float* d_normals, uint32_t nn,
+            hipStream_t stream) {
+    if (nv)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
+                           d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
+    if (d_normals && nn)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
+                           (float4*)nullptr, d_normals, nn, 0.f);
+    const uint32_t n_lanes = 4u * d.n_world_leaves;
+    if (n_lanes)
+        hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves, n_lanes, d.prims,
+                           d.verts, d.has_mb ? d.pflags : (uint8_t*)nullptr, d.refit_mbslot, d.refit_fixed, d.n_insts,
+                           d.refit_lbox);
+    for (size_t h = 0; h + 1 < d.refit_off.size(); h++) {
+        const uint32_t n = d.refit_off[h + 1] - d.refit_off[h];
+        if (!n) continue;
+        hipLaunchKernelGGL(refit_node_kernel, blocks((size_t)4 * n), dim3(kRefitWG), 0, stream, d.nodes,
+                           d.refit_order + d.refit_off[h], n, d.refit_lbox);
+    }
+    HIP_OK(hipGetLastError());
+    return MRT_OK;
+}
+
+}  // namespace
+
+// The host copy from replica s.dev (or the first one): node boxes and leaf triangles in
+// canonical numbers and layout, the vertices and normals of the meshes an async update left
+// on the device, and from them the binning boxes of every replica.
+int sync_host(Scene& s, bool meshes_only) {
+    if (meshes_only ? s.host_mesh_stale.empty() : !s.host_stale()) return MRT_OK;
+    DeviceState* d = s.dev ? s.dev : (s.devs.empty() ? nullptr : s.devs[0]);
+    if (!d) { set_error("refit: the device copy that is ahead of the host is gone"); return MRT_ERR_INVALID; }
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    HIP_OK(hipSetDevice(d->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (s.host_bvh_stale && !meshes_only) {
+        std::vector<QNode> DN(d->n_world_nodes);
+        std::vector<DLeaf> DL(d->n_world_leaves);
+        HIP_OK(hipMemcpy(DN.data(), d->nodes, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
+        if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d->leaves, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < s.nodes.size() && i < DN.size(); i++)
+            memcpy(s.nodes[i].box, DN[d->node_perm.empty() ? i : (size_t)d->node_perm[i]].box, sizeof s.nodes[i].box);
+        for (size_t i = 0; i < s.leaves.size() && i < DL.size(); i++)
+            for (int k = 0; k < 4; k++)
+                for (int c = 0; c < 9; c++) s.leaves[i].t[4 * c + k] = DL[i].tri[k][c];
+    }
+    for (int32_t m : s.host_mesh_stale) {
+        Mesh& M = s.meshes[(size_t)m];
+        std::vector<float4> buf(std::max(M.verts.size(), M.normals.size()));
+        if (!M.verts.empty()) HIP_OK(hipMemcpy(buf.data(), d->verts + d->vbase[(size_t)m], M.verts.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < M.verts.size(); i++) M.verts[i] = mk(buf[i].x, buf[i].y, buf[i].z);
+        if (!M.normals.empty()) HIP_OK(hipMemcpy(buf.data(), d->normals + d->nbase[(size_t)m], M.normals.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < M.normals.size(); i++) M.normals[i] = mk(buf[i].x, buf[i].y, buf[i].z);
+    }
+    s.host_mesh_stale.clear();
+    if (!meshes_only) s.host_bvh_stale = false;
+    if (!meshes_only && !s.nodes.empty())
+        for (DeviceState* r : s.devs) root_box(s.nodes[0], r->bb_lo, r->bb_hi);
+    if (cur >= 0) (void)hipSetDevice(cur);
+    return MRT_OK;
+}
+
+}  // namespace mrt
+
+using namespace mrt;
+
+extern "C" {
+
+int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts, const float* normals, float* refit_ms) {
+    if (refit_ms) *refit_ms = 0.f;
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    if (!verts) { set_error("update_mesh: null vertices"); return MRT_ERR_INVALID; }
+    int rc = refit_check(S, mesh, verts, normals);   // arguments first: no device call before
+    if (rc) return rc;
+    Mesh& M = S.meshes[(size_t)mesh];
+    const bool on_device = !S.dev_dirty && !S.devs.empty();
+    if (!on_device) {   // built, not uploaded (or a re-upload is due anyway): the same arithmetic on the host
+        if ((rc = sync_host(S))) return rc;
+        refit_set_mesh(M, verts, normals);
+        refit_host(S);
+        return MRT_OK;
+    }
+    if ((rc = sync_host(S, true))) return rc;   // the host mesh is current from here (the hierarchy stays on the device)
+    refit_set_mesh(M, verts, normals);
+    const uint32_t nv = (uint32_t)M.verts.size(), nn = normals ? (uint32_t)M.normals.size() : 0u;
+    DeviceState* cur = S.dev ? S.dev : S.devs[0];
+    for (DeviceState* d : S.devs) {
+        HIP_OK(hipSetDevice(d->device));
+        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
+        if ((rc = prepare(S, *d))) return rc;
+        const size_t need = ((size_t)nv + nn) * 3;
+        if (need > d->refit_stage_cap) {
+            if (d->refit_stage) (void)hipFree(d->refit_stage);
+            d->refit_stage = nullptr;
+            d->refit_stage_cap = 0;
+            HIP_OK(hipMalloc((void**)&d->refit_stage, need * sizeof(float)));
+            d->refit_stage_cap = need;
+        }
+        if (nv) HIP_OK(hipMemcpy(d->refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (nn) HIP_OK(hipMemcpy(d->refit_stage + (size_t)nv * 3, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (!M.tidx.empty() && d->tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
+            std::vector<float4> T(M.tan.size()), B(M.btan.size());
+            for (size_t i = 0; i < T.size(); i++) T[i] = make_float4(M.tan[i].x, M.tan[i].y, M.tan[i].z, 0.f);
+            for (size_t i = 0; i < B.size(); i++) B[i] = make_float4(M.btan[i].x, M.btan[i].y, M.btan[i].z, 0.f);
+            HIP_OK(hipMemcpy(d->tans + d->nbase[(size_t)mesh], T.data(), T.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d->btans + d->nbase[(size_t)mesh], B.data(), B.size() * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
+        if ((rc = enqueue(*d, mesh, d->refit_stage, nv, nn ? d->refit_stage + (size_t)nv * 3 : nullptr, nn, nullptr))) return rc;
+        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
+        HIP_OK(hipEventSynchronize(d->refit_ev1));
+        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
+        QNode root;   // the binning box follows the refitted root
+        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
+        root_box(root, d->bb_lo, d->bb_hi);
+    }
+    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
+    HIP_OK(hipSetDevice(cur->device));
+    return MRT_OK;
+}
+
+int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_normals, void* stream) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    int rc = refit_check(S, mesh, nullptr, nullptr);
+    if (rc) return rc;
+    if (!d_verts) { set_error("update_mesh: null vertices"); return MRT_ERR_INVALID; }
+    Mesh& M = S.meshes[(size_t)mesh];
+    if (!M.tidx.empty()) {
+        set_error("update_mesh_async: the mesh has texture coordinates (its tangent frames are recomputed on the host: use mrt_scene_update_mesh)");
+        return MRT_ERR_INVALID;
+    }
+    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
+        set_error("update_mesh_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
+        return MRT_ERR_INVALID;
+    }
+    DeviceState& d = *S.dev;
+    HIP_OK(hipSetDevice(d.device));
+    if ((rc = prepare(S, d))) return rc;
+    if ((rc = enqueue(d, mesh, d_verts, (uint32_t)M.verts.size(), d_normals, (uint32_t)M.normals.size(), (hipStream_t)stream)))
+        return rc;
+    S.host_bvh_stale = true;
+    if (std::find(S.host_mesh_stale.begin(), S.host_mesh_stale.end(), mesh) == S.host_mesh_stale.end())
+        S.host_mesh_stale.push_back(mesh);
+    return MRT_OK;
+}
+
+}  // extern "C"

@@ -110,6 +110,15 @@ struct Scene {
     std::vector<QLeaf> leaves;
     mrt_bvh_info info{};
     bool built = false;
+    bool imported = false;   // nodes / leaves came from mrt_scene_bvh_import (may be a DAG: no refit)
+
+    // mrt_scene_update_mesh on an uploaded scene refits on the device only: the replicas'
+    // node boxes and leaf triangles are then ahead of nodes / leaves (host_bvh_stale), and
+    // after the async form the vertices and normals of host_mesh_stale's meshes too.
+    // sync_host (mrt_refit.hip) reads them back before anything reads the host copy.
+    bool host_bvh_stale = false;
+    std::vector<int32_t> host_mesh_stale;
+    bool host_stale() const { return host_bvh_stale || !host_mesh_stale.empty(); }
 
     // device replicas (one per HIP device used, mrt_render_opts.devices); `dev` is
     // the one the last call used.  dev_dirty: the host scene changed, every
@@ -129,6 +138,20 @@ int load_obj(const char* path, const float* ctm16, Mesh& out, std::string& err);
 int build_qbvh(Scene& s, std::string& err);
 int make_blas(Scene& s, const int32_t* meshes, int n_meshes, std::string& err);
 int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err);
+// The refit on the host: the world leaf triangles from the meshes' vertices (make_leaf),
+// then every box bottom-up, topology kept (the arithmetic of mrt_refit.hip's kernels).
+void refit_host(Scene& s);
+// The box the build gave world object o when it is a ProxyObject or an MBObject lane
+// (Builder::tri_aabb): min xyz, max xyz.  False for a plain triangle.
+bool fixed_lane_box(const Scene& s, int32_t o, float box[6]);
+// mrt_refit.hip: bring a stale host copy up to date from the device (synchronises); a
+// no-op when nothing is stale
+// (meshes_only: the vertices and normals an async update left there, not the hierarchy)
+int sync_host(Scene& s, bool meshes_only = false);
+// host_api.cpp: the argument checks of mrt_scene_update_mesh (verts == nullptr: the async
+// form, whose arrays are on the device), and the new arrays into the host mesh
+int refit_check(const Scene& s, int mesh, const float* verts, const float* normals);
+void refit_set_mesh(Mesh& m, const float* verts, const float* normals);
 // host_texture.cpp
 int load_hdr(const char* path, int& W, int& H, std::vector<float>* rgb, std::string& err);
 int build_dome(const Texture& t, DomeTables& d, std::string& err);

@@ -44,6 +44,9 @@ static void free_device(DeviceState* d) {
     }
     if (d->g_tiles) (void)hipFree(d->g_tiles);
     if (d->g_items) (void)hipFree(d->g_items);
+    if (d->refit_stage) (void)hipFree(d->refit_stage);
+    if (d->refit_ev0) (void)hipEventDestroy(d->refit_ev0);
+    if (d->refit_ev1) (void)hipEventDestroy(d->refit_ev1);
     void* ptrs[] = {d->nodes, d->leaves, d->prims, d->verts, d->normals, d->mats, d->lights, d->domes, d->insts,
                     d->inst_hit_base, d->inst_class, d->inst_cell, d->tables,
                     d->gamma, d->gammaF, d->d_rgb, d->d_rgb8, d->texs, d->puv, d->uvs, d->tans, d->btans,
@@ -94,9 +97,14 @@ void free_replicas(Scene& s) {
 // dropped when the host scene changed) becomes s.dev.
 int ensure_device(Scene& s, int device) {
     if (!s.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
-    if (s.dev_dirty) { free_replicas(s); s.dev_dirty = false; }
+    if (s.dev_dirty) {
+        if (const int rc = sync_host(s)) return rc;   // a device refit is ahead of the host copy the re-upload reads
+        free_replicas(s);
+        s.dev_dirty = false;
+    }
     for (DeviceState* d : s.devs)
         if (d->device == device) { s.dev = d; return MRT_OK; }
+    if (const int rc = sync_host(s)) return rc;   // a second device is uploaded from the host copy
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device"); return MRT_ERR_NO_DEVICE; }
     if (device < 0 || device >= n) { set_error("bad device ordinal"); return MRT_ERR_INVALID; }
@@ -107,6 +115,22 @@ int ensure_device(Scene& s, int device) {
     s.devs.push_back(d);
     s.dev = d;
     return MRT_OK;
+}
+
+// union of the root's used slot boxes (finite values only, per axis)
+void root_box(const QNode& root, float lo3[3], float hi3[3]) {
+    for (int a = 0; a < 3; a++) lo3[a] = hi3[a] = 0.f;
+    bool any[3] = {false, false, false};
+    for (int i = 0; i < 4; i++) {
+        if (root.child[i] == kEmptySlot) continue;
+        for (int a = 0; a < 3; a++) {
+            const float lo = root.box[a * 4 + i], hi = root.box[12 + a * 4 + i];
+            if (!std::isfinite(lo) || !std::isfinite(hi)) continue;
+            lo3[a] = any[a] ? std::min(lo3[a], lo) : lo;
+            hi3[a] = any[a] ? std::max(hi3[a], hi) : hi;
+            any[a] = true;
+        }
+    }
 }
 
 static int upload_scene(Scene& s, DeviceState& d, int device) {
@@ -286,7 +310,12 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
         }
         DN.swap(R);
         for (int32_t& br : blas_root) br = perm[(size_t)br];
+        d.node_perm.assign(perm.begin(), perm.begin() + (ptrdiff_t)nw);
     }
+    d.n_world_nodes = (uint32_t)nw;
+    d.n_world_leaves = (uint32_t)s.leaves.size();
+    d.vbase = vbase;
+    d.nbase = nbase;
     for (QNode& q : DN) q.pad[0] = slot_kinds(q.child);   // the walks read the slot kinds (node_kinds)
     if (!walk_arrays_fit(DN.size(), DL.size())) {   // 32-bit byte offsets in the walks (node_at / tri_at)
         set_error("scene too large: its node or leaf array passes 4 GiB");
@@ -418,20 +447,7 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
             if (q.child[i] != kEmptySlot)
                 for (int a = 0; a < 3; a++) d.boxes_ordered &= q.box[a * 4 + i] <= q.box[12 + a * 4 + i];
     }
-    for (int a = 0; a < 3; a++) d.bb_lo[a] = d.bb_hi[a] = 0.f;
-    if (!DN.empty()) {   // union of the root's used slot boxes (finite values only, per axis)
-        bool any[3] = {false, false, false};
-        for (int i = 0; i < 4; i++) {
-            if (DN[0].child[i] == kEmptySlot) continue;
-            for (int a = 0; a < 3; a++) {
-                const float lo = DN[0].box[a * 4 + i], hi = DN[0].box[12 + a * 4 + i];
-                if (!std::isfinite(lo) || !std::isfinite(hi)) continue;
-                d.bb_lo[a] = any[a] ? std::min(d.bb_lo[a], lo) : lo;
-                d.bb_hi[a] = any[a] ? std::max(d.bb_hi[a], hi) : hi;
-                any[a] = true;
-            }
-        }
-    }
+    if (!DN.empty()) root_box(DN[0], d.bb_lo, d.bb_hi);
     d.point_only = true;
     d.dome = false;
     for (const DevLight& l : s.lights) {

@@ -706,6 +706,42 @@ class Scene:
                                          lp.ctypes.data_as(C.POINTER(C.c_int32))), "bvh_export")
         return nb, nc, lt, lp
 
+    # -- geometry that moves between frames (no reference counterpart: it rebuilds)
+    def updateMesh(self, mesh_id: int, verts, normals=None, stream=None):
+        """New vertices (and normals) for world mesh `mesh_id`, same counts and topology, and
+        the hierarchy refitted in place (mrt_scene_update_mesh): the tree keeps its topology,
+        so its quality degrades under large deformation and preCalc() remains the remedy.
+        numpy arrays ((nv, 3) / (nn, 3)) go through the synchronous entry, which returns the
+        device time of the refit kernels in ms (0.0 for a scene not yet uploaded: the host
+        refits).  torch device tensors (contiguous float32 on the scene's device) go through
+        mrt_scene_update_mesh_async on `stream` (a torch stream; default: the current one)
+        without a host copy or a synchronisation (once the scene is on its device: a scene
+        not yet uploaded is uploaded first), and return None; the mesh must have no texture
+        coordinates."""
+        L = lib()
+        nv, nn, nt = C.c_int32(), C.c_int32(), C.c_int32()
+        check(L.mrt_scene_mesh_info(self.handle, int(mesh_id), C.byref(nv), C.byref(nn), C.byref(nt)), "updateMesh")
+        for x, n, what in ((verts, nv.value, "verts"), (normals, nn.value, "normals")):
+            if x is not None and int(np.prod(tuple(x.shape))) != 3 * n:
+                raise MRTError(f"updateMesh: {what} must hold {n} x 3 floats (the mesh's own count)")
+        if hasattr(verts, "data_ptr"):
+            import torch
+            for x in (verts, normals):
+                if x is not None and not (hasattr(x, "data_ptr") and x.is_cuda and x.dtype == torch.float32
+                                          and x.is_contiguous() and x.device.index == self.device):
+                    raise MRTError("updateMesh: tensors must be contiguous float32 on the scene's device")
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            st = (stream if stream is not None else torch.cuda.current_stream(verts.device)).cuda_stream
+            check(L.mrt_scene_update_mesh_async(self.handle, int(mesh_id), verts.data_ptr(),
+                                                normals.data_ptr() if normals is not None else None, st), "updateMesh")
+            return None
+        v = np.ascontiguousarray(verts, np.float32)
+        n = np.ascontiguousarray(normals, np.float32) if normals is not None else None
+        ms = C.c_float(0.0)
+        check(L.mrt_scene_update_mesh(self.handle, int(mesh_id), v.ctypes.data, n.ctypes.data if n is not None else None,
+                                      C.byref(ms)), "updateMesh")
+        return float(ms.value)
+
     # -- rendering (src/Scene.cpp:85-217)
     def raytraceImage(self, cam: Camera, img: Image, count_visits=False, want_hits=False, seed=0, devices=None):
         """devices: HIP device ordinals to deal the 32x32 buckets over (bucket b ->

@@ -31,7 +31,7 @@ EXPORTS = [
     "mrt_render_batch_frames_async", "mrt_ipc_export", "mrt_ipc_open", "mrt_ipc_close", "mrt_get_tuning",
     "mrt_walk_arrays_fit", "mrt_sample_rays", "mrt_sample_rays_async", "mrt_camera_rays",
     "mrt_trace_rays", "mrt_trace_rays_async", "mrt_shade_hits", "mrt_shade_hits_async", "mrt_hit_surfaces",
-    "mrt_hit_surfaces_async",
+    "mrt_hit_surfaces_async", "mrt_scene_update_mesh", "mrt_scene_update_mesh_async",
 ]
 
 
@@ -211,6 +211,9 @@ def load():
         L.mrt_shade_hits_async.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_int32, C.c_uint32, C.c_int32, vp, vp]
         L.mrt_hit_surfaces.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
         L.mrt_hit_surfaces_async.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "mrt_scene_update_mesh"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_scene_update_mesh.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.mrt_scene_update_mesh_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
