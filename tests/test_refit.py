@@ -86,9 +86,10 @@ def assert_arrays(got, want):
         assert np.array_equal(g, w), f"{name} differ in {int((g != w).sum())} values"
 
 
-def refit_of(export, prim_verts, fixed_boxes=None):
+def refit_of(export, prim_verts, fixed_boxes=None, arrays=None):
+    """arrays: another form of refit_arrays (test_refit_shapes.py has one vectorised per height)."""
     nb, nc, lt, lp = export
-    rb, rt = refit_arrays(nb, nc, lt, lp, prim_verts, fixed_boxes)
+    rb, rt = (arrays or refit_arrays)(nb, nc, lt, lp, prim_verts, fixed_boxes)
     return rb, nc, rt, lp
 
 
@@ -111,10 +112,12 @@ def tri_mesh(V, N, F):
     return tm
 
 
-def floor_mesh():
+def floor_mesh(verts=None):
     fl = miro.TriangleMesh()
     fl.createSingleTriangle()
     fl.setV1((-100, 0, -100)); fl.setV2((0, 0, 100)); fl.setV3((100, 0, -100))
+    if verts is not None:
+        fl.verts[:] = verts
     fl.setN1((0, 1, 0)); fl.setN2((0, 1, 0)); fl.setN3((0, 1, 0))
     return fl
 
@@ -169,24 +172,28 @@ def displaced(V, F, seed, amp=0.3):
     return V1, np.asarray(scenes._smooth_normals(V1.astype(np.float64), F.astype(np.int64)), F32)
 
 
-def scene_a(V, N, F, light=point_light, num_paths=1, material=None, uv=None):
-    """The stand-in (mesh 0), a floor (mesh 1) and a light."""
+def scene_a(V, N, F, light=point_light, num_paths=1, material=None, uv=None, floor=None, path_trace=None):
+    """The stand-in (mesh 0), a floor (mesh 1; floor: its three vertices) and a light.
+    path_trace: max bounces, turns Scene::m_pathTrace on."""
     P = miro.Scene()
     mat = material or miro.Lambert((0.8, 0.7, 0.6))
     tm = tri_mesh(V, N, F)
     if uv is not None:
         tm.setTexCoords(uv, F)
     miro.makeMeshObjs(P, tm, mat)
-    miro.makeMeshObjs(P, floor_mesh(), miro.Lambert((0.6, 0.6, 0.6)))
+    miro.makeMeshObjs(P, floor_mesh(floor), miro.Lambert((0.6, 0.6, 0.6)))
     P.addLight(light())
     P.setBGColor((0.1, 0.1, 0.3))
     P.setNumPaths(num_paths)
+    if path_trace is not None:
+        P.setPathTrace(True)
+        P.setMaxBounces(path_trace)
     P.preCalc()
     return P
 
 
-def a_prim_verts(V, F):
-    fl = floor_mesh()
+def a_prim_verts(V, F, floor=None):
+    fl = floor_mesh(floor)
     return prim_verts_of((V, F), (fl.verts, fl.vidx))
 
 
@@ -195,6 +202,9 @@ def import_bvh(P, arrays):
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     _lib.check(miro.lib().mrt_scene_bvh_import(P.handle, len(nb), len(lt), nb.ctypes.data_as(fp), nc.ctypes.data_as(ip),
                                                lt.ctypes.data_as(fp), lp.ctypes.data_as(ip)), "bvh_import")
+    info = _lib.mrt_bvh_info()   # a later P.bvh_export() sizes its arrays by these counts
+    _lib.check(miro.lib().mrt_scene_bvh_info(P.handle, C.byref(info)), "bvh_info")
+    P.bvh_info = {k: getattr(info, k) for k, _ in info._fields_}
 
 
 def update_rc(P, mesh, verts, normals=None):
@@ -209,7 +219,8 @@ def frame(P, W=96, H=96, cam=CAM):
     img = miro.Image()
     img.resize(W, H)
     hits = P.raytraceImage(camera(cam), img, want_hits=True)
-    return dict(rgb=img.rgb.copy(), rgb8=img.pixels.copy(), hits=hits.copy(), shadow_rays=P.last_stats["shadow_rays"])
+    return dict(rgb=img.rgb.copy(), rgb8=img.pixels.copy(), hits=hits.copy(), shadow_rays=P.last_stats["shadow_rays"],
+                secondary_rays=P.last_stats["secondary_rays"])
 
 
 def assert_frames(a, b):
@@ -250,9 +261,10 @@ def instance_box(root_boxes, M):
     return nlo, nhi
 
 
-def mixed_scene(V, N, F, moving=True):
+def mixed_scene(V, N, F, moving=True, later=None):
     """The stand-in (mesh 0), two instances of a small sphere (mesh 1), a small motion-blurred
-    sphere (mesh 2; moving only) and a floor.  Returns (scene, prim_verts, fixed_boxes)."""
+    sphere (mesh 2; moving only), a static mesh after it (later: its (V, N, F)) and a floor.
+    Returns (scene, prim_verts, fixed_boxes)."""
     P = miro.Scene()
     miro.makeMeshObjs(P, tri_mesh(V, N, F), miro.Lambert((0.8, 0.7, 0.6)))
     bV, bN, bF = blas_mesh()
@@ -266,6 +278,9 @@ def mixed_scene(V, N, F, moving=True):
         mV2 = np.asarray(mV + np.array([0.35, 0.1, 0.0], F32), F32)
         miro.makeMBMeshObjs(P, tri_mesh(mV, bN, bF), tri_mesh(mV2, bN, bF), miro.Lambert((0.9, 0.4, 0.3)))
         entries.append((mV, bF))
+    if later is not None:
+        miro.makeMeshObjs(P, tri_mesh(*later), miro.Lambert((0.4, 0.5, 0.9)))
+        entries.append((later[0], later[2]))
     fl = floor_mesh()
     miro.makeMeshObjs(P, fl, miro.Lambert((0.6, 0.6, 0.6)))
     entries.append((fl.verts, fl.vidx))
