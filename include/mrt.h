@@ -360,7 +360,8 @@ int mrt_scene_upload(mrt_scene* s, int device);
  *    or a motion-blurred mesh returns MRT_ERR_INVALID (a BLAS refit moves the instance
  *    box and the world tree above it; an MBObject lane's box needs both vertex sets).
  *    Scenes that hold instances or motion-blurred meshes beside the updated mesh are
- *    fine: their leaf lanes keep the box the build gave them.
+ *    fine: a ProxyObject lane keeps the box it has now (the build's, or the one
+ *    mrt_scene_update_instances gave it since), an MBObject lane the build's.
  *  - a scene whose hierarchy came from mrt_scene_bvh_import (it may share nodes between
  *    parents) returns MRT_ERR_INVALID; an unbuilt scene MRT_ERR_NOT_BUILT.
  *  - arguments are checked before any device call; every vertex and normal must be
@@ -383,6 +384,45 @@ int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts,
  * device first read the device state back, synchronising. */
 int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts,
                                 const float* d_normals, void* stream);
+
+/* ---- instances that move between frames: ProxyMatrix::set (src/ProxyMatrix.cpp:17-22)
+ * for instances of a built scene, followed by a refit where the reference rebuilds.
+ * m16s holds n row-major 4x4 m_transform matrices for the instances ids[0 .. n)
+ * (ids == NULL: instances 0 .. n-1).  Per instance m_transform, m_inverse, m_invTranspose
+ * and the ProxyObject::getAABB box are recomputed exactly as mrt_scene_add_instance does,
+ * then the world hierarchy is refitted on every uploaded replica as mrt_scene_update_mesh
+ * does: the topology, the BLAS arrays and every hit id stay.  On the device one kernel
+ * restates the host arithmetic bit for bit (DESIGN.md "Instance refit").
+ * *refit_ms (nullable): device time of the kernels on the current device.  n == 0: MRT_OK.
+ *  - every argument is checked before any device call and before any change: a batch is
+ *    all or nothing.  MRT_ERR_INVALID for a null scene or null matrices, a hierarchy from
+ *    mrt_scene_bvh_import, an id out of range or repeated in the batch (the id is in
+ *    mrt_last_error), a matrix with an entry that is not finite, and a matrix whose
+ *    computed inverse or box is not finite, which covers a singular one (mrt_last_error
+ *    names its position in the batch); MRT_ERR_NOT_BUILT for an unbuilt scene.
+ *  - a scene that is built but not uploaded (or due for a re-upload) is updated and
+ *    refitted on the host: the same arithmetic.
+ * Out of scope: new vertices for a mesh of a BLAS (a BLAS refit, then this call),
+ * motion-blurred meshes, adding or removing instances, changing an instance's BLAS, any
+ * rebuild heuristic (tree quality degrades as instances travel; mrt_scene_build_bvh on a
+ * new scene remains the remedy), and the shim. */
+int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n,
+                               const float* m16s, float* refit_ms);
+/* The same for the contiguous range [first, first + n) with the matrices on the device,
+ * enqueued on `stream`, never synchronising (the first refit of a replica allocates and
+ * uploads its schedule).  The range is checked on the host; the matrices are not checked:
+ * they must be finite and invertible.  It needs the scene uploaded to exactly one device
+ * (else MRT_ERR_INVALID).  The host copy is left stale: mrt_scene_bvh_export,
+ * mrt_scene_instance_info, a host refit, a re-upload after a scene change and an upload
+ * to a second device first read the device state back, synchronising. */
+int mrt_scene_update_instances_async(mrt_scene* s, int32_t first, int32_t n,
+                                     const float* d_m16s, void* stream);
+/* What an instance holds now: its BLAS id, m_transform, m_inverse, m_invTranspose
+ * (row-major 4x4 each) and its ProxyObject::getAABB box (min xyz, max xyz); every output
+ * is nullable.  After an async update it reads the device state back (synchronises). */
+int mrt_scene_instance_count(const mrt_scene* s);
+int mrt_scene_instance_info(const mrt_scene* s, int32_t inst, int32_t* blas, float m16[16],
+                            float inv16[16], float inv_t16[16], float box6[6]);
 
 /* ---- frame entry: Scene::raytraceImage(Camera*, Image*) (src/Scene.cpp:85-217).
  * Synchronous, host buffers: rgb (W*H*3 floats, before Map) and rgb8 (W*H*3,

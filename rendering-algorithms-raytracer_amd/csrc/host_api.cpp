@@ -104,6 +104,52 @@ void refit_set_mesh(Mesh& m, const float* verts, const float* normals) {
     mesh_tangents(m);   // TriangleMesh::preCalc of a texture-mapped mesh
 }
 
+// mrt_scene_update_instances / _async (mrt_refit.hip): which scenes, ids and matrices it takes
+int instances_check(const Scene& S, const int32_t* ids, int32_t first, int32_t n, const float* m16s,
+                    std::vector<Instance>* out) {
+    if (!S.built) { set_error("update_instances: scene not built"); return MRT_ERR_NOT_BUILT; }
+    if (S.imported) {
+        set_error("update_instances: the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
+        return MRT_ERR_INVALID;
+    }
+    const int64_t ni = (int64_t)S.instances.size();
+    if (n < 0) { set_error("update_instances: negative count"); return MRT_ERR_INVALID; }
+    if (!ids && (first < 0 || (int64_t)first + n > ni)) {
+        set_error("update_instances: instance id " + std::to_string(first < 0 ? (int64_t)first : ni) + " out of range (the scene has " +
+                  std::to_string(ni) + " instances)");
+        return MRT_ERR_INVALID;
+    }
+    std::vector<char> seen(ids ? (size_t)ni : 0, 0);
+    for (int32_t k = 0; ids && k < n; k++) {
+        if (ids[k] < 0 || ids[k] >= ni) {
+            set_error("update_instances: instance id " + std::to_string(ids[k]) + " out of range (the scene has " + std::to_string(ni) +
+                      " instances)");
+            return MRT_ERR_INVALID;
+        }
+        if (seen[(size_t)ids[k]]++) {
+            set_error("update_instances: instance id " + std::to_string(ids[k]) + " repeated in the batch");
+            return MRT_ERR_INVALID;
+        }
+    }
+    if (!m16s) return MRT_OK;
+    if (out) out->clear();
+    for (int32_t k = 0; k < n; k++) {
+        const float* m = m16s + 16 * (size_t)k;
+        const int32_t id = ids ? ids[k] : first + k;
+        const std::string which = "update_instances: matrix " + std::to_string(k) + " (instance " + std::to_string(id) + ")";
+        for (int j = 0; j < 16; j++)
+            if (!std::isfinite(m[j])) { set_error(which + " has an entry that is not finite"); return MRT_ERR_INVALID; }
+        Instance I = S.instances[(size_t)id];
+        instance_set_matrix(S, I, m);
+        bool ok = true;
+        for (int j = 0; j < 16; j++) ok = ok && std::isfinite(I.inv[j]);
+        for (int j = 0; j < 6; j++) ok = ok && std::isfinite(I.box[j]);
+        if (!ok) { set_error(which + " is singular or nearly so: its inverse or box is not finite"); return MRT_ERR_INVALID; }
+        if (out) out->push_back(I);
+    }
+    return MRT_OK;
+}
+
 }  // namespace mrt
 
 using namespace mrt;
@@ -624,6 +670,26 @@ int mrt_scene_bvh_export(const mrt_scene* s, float* node_boxes, int32_t* node_ch
         memcpy(leaf_tris + 36 * i, s->impl.leaves[i].t, 144);
         memcpy(leaf_prims + 4 * i, s->impl.leaves[i].prim, 16);
     }
+    return MRT_OK;
+}
+
+int mrt_scene_instance_count(const mrt_scene* s) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    return (int)s->impl.instances.size();
+}
+
+int mrt_scene_instance_info(const mrt_scene* s, int32_t inst, int32_t* blas, float m16[16], float inv16[16], float inv_t16[16],
+                            float box6[6]) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (inst < 0 || (size_t)inst >= s->impl.instances.size()) { set_error("bad instance id"); return MRT_ERR_INVALID; }
+    // after an async update: the matrices and the box the device holds, read back
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl, true)) return rc;
+    const Instance& I = s->impl.instances[(size_t)inst];
+    if (blas) *blas = I.blas;
+    if (m16) memcpy(m16, I.m, sizeof I.m);
+    if (inv16) memcpy(inv16, I.inv, sizeof I.inv);
+    if (inv_t16) memcpy(inv_t16, I.inv_t, sizeof I.inv_t);
+    if (box6) memcpy(box6, I.box, sizeof I.box);
     return MRT_OK;
 }
 

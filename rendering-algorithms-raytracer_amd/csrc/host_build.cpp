@@ -1204,17 +1204,17 @@ int make_blas(Scene& s, const int32_t* meshes, int n_meshes, std::string& err) {
 // src/ProxyMatrix.cpp:3-8) and ProxyObject::getAABB (src/ProxyObject.cpp:45-72):
 // the BLAS root box (QBVH_Node::getAABB: the union of all four slots, unused ones
 // included as zero boxes, src/BVH.cpp:107-112,416-424), corners A..F, bbMin,
-// bbMax through multiplyAndDivideByW, grown in that order.
-int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err) {
-    if (!m16 || blas < 0 || blas >= (int32_t)s.blas.size()) { err = "bad BLAS id or matrix"; return MRT_ERR_INVALID; }
-    Instance I{};
+// bbMax through multiplyAndDivideByW, grown in that order.  instance_set_matrix is that
+// arithmetic for I.blas (also ProxyMatrix::set, src/ProxyMatrix.cpp:17-22: mrt_refit.hip's
+// refit_instance_kernel restates it on the device, bit for bit).
+void instance_set_matrix(const Scene& s, Instance& I, const float* m16) {
+    const int32_t blas = I.blas;
     Mat4 M;
     memcpy(M.m, m16, sizeof M.m);
     const Mat4 inv = inverse(M), inv_t = transpose(inverse(M));
     memcpy(I.m, M.m, sizeof I.m);
     memcpy(I.inv, inv.m, sizeof I.inv);
     memcpy(I.inv_t, inv_t.m, sizeof I.inv_t);
-    I.blas = blas;
     const QNode& r = s.blas[blas].nodes[0];
     Box t = empty_box();
     for (int k = 0; k < 4; k++)
@@ -1231,6 +1231,13 @@ int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err) {
         I.box[k] = nb.mn[k];
         I.box[3 + k] = nb.mx[k];
     }
+}
+
+int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err) {
+    if (!m16 || blas < 0 || blas >= (int32_t)s.blas.size()) { err = "bad BLAS id or matrix"; return MRT_ERR_INVALID; }
+    Instance I{};
+    I.blas = blas;
+    instance_set_matrix(s, I, m16);
     s.instances.push_back(I);
     s.groups.push_back(~(int32_t)(s.instances.size() - 1));
     s.built = false;

@@ -224,6 +224,7 @@ struct DeviceState {
     float4* refit_lbox = nullptr;         // per world packet: box min xyz, max xyz (2 float4; one of bufs)
     float4* refit_fixed = nullptr;        // ProxyObject lanes' boxes by instance, then MBObject lanes' (2 float4 each)
     int32_t* refit_mbslot = nullptr;      //   per world prim: its MBObject box after the instances', -1 = none
+    float* refit_inst_m = nullptr;        // per instance: m_transform, 16 floats (refit_instance_kernel keeps it current; one of bufs)
     float* refit_stage = nullptr;         // the synchronous entry's packed vertices / normals on the device
     size_t refit_stage_cap = 0;           //   floats
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;

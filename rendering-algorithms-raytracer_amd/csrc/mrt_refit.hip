@@ -4,6 +4,9 @@
 // launch per height, deepest first.  Every box is a min / max merge in a fixed order
 // (mrt_math.h std_min / std_max, as Builder::tri_aabb and merge): the result is stated bit
 // for bit by refit_host (host_build.cpp) and by tests/test_refit.py's numpy restatement.
+// mrt_scene_update_instances: new matrices for ProxyObject instances; one kernel restates
+// add_instance's arithmetic per instance (inverse, inverse transpose, box), then the same
+// leaf and node kernels.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(kRefitWG) void refit_leaf_kernel(DLeaf* __restrict_
     int used = 0;
     if (in) {
         const int32_t prim = leaves[leaf].prim[k];
-        int fx = -1;   // a ProxyObject / MBObject lane: its box of the build
+        int fx = -1;   // a ProxyObject lane: its instance's box now; an MBObject lane: its box of the build
         if (prim <= -2) fx = -2 - prim;
         else if (prim >= 0 && pflags && (pflags[prim] & 1u)) fx = n_insts + mbslot[prim];
         if (fx >= 0) {
@@ -128,6 +131,94 @@ __global__ __launch_bounds__(kRefitWG) void refit_node_kernel(QNode* __restrict_
     q->box[12 + k] = b.hi[0]; q->box[16 + k] = b.hi[1]; q->box[20 + k] = b.hi[2];
 }
 
+// Matrix4x4::invert as inverse() of host_build.cpp states it, operation for operation: the 18
+// 2x2 terms, the 16 3x3 sums, det, 1 / det in double (a correctly rounded f64 divide, then
+// one rounding to float) and the signed cofactors times it.
+__device__ void d_inverse(const float (&a)[4][4], float (&R)[4][4]) {
+    auto t2 = [](float p, float q, float r, float s) { return p * q - r * s; };
+    const float T34_12 = t2(a[2][0], a[3][1], a[2][1], a[3][0]), T34_13 = t2(a[2][0], a[3][2], a[2][2], a[3][0]);
+    const float T34_14 = t2(a[2][0], a[3][3], a[2][3], a[3][0]), T34_23 = t2(a[2][1], a[3][2], a[2][2], a[3][1]);
+    const float T34_24 = t2(a[2][1], a[3][3], a[2][3], a[3][1]), T34_34 = t2(a[2][2], a[3][3], a[2][3], a[3][2]);
+    const float T24_12 = t2(a[1][0], a[3][1], a[1][1], a[3][0]), T24_13 = t2(a[1][0], a[3][2], a[1][2], a[3][0]);
+    const float T24_14 = t2(a[1][0], a[3][3], a[1][3], a[3][0]), T24_23 = t2(a[1][1], a[3][2], a[1][2], a[3][1]);
+    const float T24_24 = t2(a[1][1], a[3][3], a[1][3], a[3][1]), T24_34 = t2(a[1][2], a[3][3], a[1][3], a[3][2]);
+    const float T23_12 = t2(a[1][0], a[2][1], a[1][1], a[2][0]), T23_13 = t2(a[1][0], a[2][2], a[1][2], a[2][0]);
+    const float T23_14 = t2(a[1][0], a[2][3], a[1][3], a[2][0]), T23_23 = t2(a[1][1], a[2][2], a[1][2], a[2][1]);
+    const float T23_24 = t2(a[1][1], a[2][3], a[1][3], a[2][1]), T23_34 = t2(a[1][2], a[2][3], a[1][3], a[2][2]);
+    auto s3 = [](float p, float q, float r, float s, float u, float v) { return p * q - r * s + u * v; };
+    const float sd[4][4] = {
+        {s3(a[1][1], T34_34, a[1][2], T34_24, a[1][3], T34_23), s3(a[1][0], T34_34, a[1][2], T34_14, a[1][3], T34_13),
+         s3(a[1][0], T34_24, a[1][1], T34_14, a[1][3], T34_12), s3(a[1][0], T34_23, a[1][1], T34_13, a[1][2], T34_12)},
+        {s3(a[0][1], T34_34, a[0][2], T34_24, a[0][3], T34_23), s3(a[0][0], T34_34, a[0][2], T34_14, a[0][3], T34_13),
+         s3(a[0][0], T34_24, a[0][1], T34_14, a[0][3], T34_12), s3(a[0][0], T34_23, a[0][1], T34_13, a[0][2], T34_12)},
+        {s3(a[0][1], T24_34, a[0][2], T24_24, a[0][3], T24_23), s3(a[0][0], T24_34, a[0][2], T24_14, a[0][3], T24_13),
+         s3(a[0][0], T24_24, a[0][1], T24_14, a[0][3], T24_12), s3(a[0][0], T24_23, a[0][1], T24_13, a[0][2], T24_12)},
+        {s3(a[0][1], T23_34, a[0][2], T23_24, a[0][3], T23_23), s3(a[0][0], T23_34, a[0][2], T23_14, a[0][3], T23_13),
+         s3(a[0][0], T23_24, a[0][1], T23_14, a[0][3], T23_12), s3(a[0][0], T23_23, a[0][1], T23_13, a[0][2], T23_12)}};
+    const float det = a[0][0] * sd[0][0] - a[0][1] * sd[0][1] + a[0][2] * sd[0][2] - a[0][3] * sd[0][3];
+    const float di = (float)(1.0 / (double)det);
+    // R(r,c) = (-1)^(r+c) * sd[c][r] * di
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) R[r][c] = (((r + c) & 1) ? -sd[c][r] : sd[c][r]) * di;
+}
+
+// DPPS 0xFF on (x, y, z, 1): (p0 + p1) + (p2 + p3)
+__device__ __forceinline__ float d_dp4(const float (&row)[4], float x, float y, float z) {
+    const float p0 = row[0] * x, p1 = row[1] * y, p2 = row[2] * z, p3 = row[3] * 1.0f;
+    return (p0 + p1) + (p2 + p3);
+}
+
+// ProxyObject::getAABB as add_instance states it: the BLAS root's four slot boxes merged from
+// the empty box (unused zero boxes included), the corners A..F, bbMin, bbMax through
+// multiplyAndDivideByW (xform_point: rcp_nr of the w dot, three multiplies), grown in order.
+__device__ DBox d_instance_box(const float (&m)[4][4], const QNode& r, const uint16_t* __restrict__ rcpT) {
+    DBox t = d_empty_box();
+    for (int k = 0; k < 4; k++)
+        t = d_merge(t, DBox{{r.box[0 + k], r.box[4 + k], r.box[8 + k]}, {r.box[12 + k], r.box[16 + k], r.box[20 + k]}});
+    const float* lo = t.lo;
+    const float* hi = t.hi;
+    const float P[8][3] = {{lo[0], lo[1], hi[2]}, {lo[0], hi[1], lo[2]}, {hi[0], lo[1], lo[2]}, {lo[0], hi[1], hi[2]},
+                           {hi[0], hi[1], lo[2]}, {hi[0], lo[1], hi[2]}, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+    DBox nb = d_empty_box();
+    for (int j = 0; j < 8; j++) {
+        const float x = P[j][0], y = P[j][1], z = P[j][2];
+        const float w = rcp_nr(d_dp4(m[3], x, y, z), rcpT);
+        const float q[3] = {w * d_dp4(m[0], x, y, z), w * d_dp4(m[1], x, y, z), w * d_dp4(m[2], x, y, z)};
+        nb = d_merge(nb, DBox{{q[0], q[1], q[2]}, {q[0], q[1], q[2]}});
+    }
+    return nb;
+}
+
+// ProxyMatrix::set for n instances, one lane each: lane g takes the row-major 4x4 at
+// m16s + 16 g for instance ids[g] (ids == nullptr: first + g; the host checked the ids) and
+// writes its inverse and inverse transpose into insts, the matrix into inst_m and its box
+// into the fixed boxes the leaf kernel reads.  The RCPSS table comes from global memory:
+// eight lookups per lane do not pay for staging 4 KB in LDS.
+__global__ __launch_bounds__(kRefitWG) void refit_instance_kernel(DevInstance* __restrict__ insts, float* __restrict__ inst_m,
+                                                                  float4* __restrict__ fixed,
+                                                                  const QNode* __restrict__ nodes,
+                                                                  const uint16_t* __restrict__ rcpT,
+                                                                  const float* __restrict__ m16s,
+                                                                  const int32_t* __restrict__ ids, int32_t first, uint32_t n) {
+    const uint32_t g = blockIdx.x * kRefitWG + threadIdx.x;
+    if (g >= n) return;
+    const size_t i = (size_t)(ids ? ids[g] : first + (int32_t)g);
+    float m[4][4], inv[4][4];
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) m[r][c] = m16s[(size_t)g * 16 + 4 * r + c];
+    d_inverse(m, inv);
+    DevInstance& I = insts[i];
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) {
+            I.inv[4 * r + c] = inv[r][c];
+            if (r < 3) I.inv_t[4 * r + c] = inv[c][r];
+            inst_m[i * 16 + 4 * r + c] = m[r][c];
+        }
+    const DBox b = d_instance_box(m, nodes[I.root], rcpT);
+    fixed[2 * i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
+    fixed[2 * i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+}
+
 template <typename T>
 int dev_array(DeviceState& d, T*& dst, const void* src, size_t bytes) {
     HIP_OK(hipMalloc((void**)&dst, bytes ? bytes : 16));
@@ -186,6 +277,9 @@ int prepare(const Scene& s, DeviceState& d) {
     if ((rc = dev_array(d, d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
     if ((rc = dev_array(d, d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4)))) return rc;
     if ((rc = dev_array(d, d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t)))) return rc;
+    std::vector<float> inst_m(16 * s.instances.size());   // m_transform: the device keeps inv / inv_t only
+    for (size_t i = 0; i < s.instances.size(); i++) memcpy(&inst_m[16 * i], s.instances[i].m, 16 * sizeof(float));
+    if ((rc = dev_array(d, d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float)))) return rc;
     HIP_OK(hipMalloc((void**)&d.refit_lbox, std::max<size_t>(1, s.leaves.size()) * 2 * sizeof(float4)));
     d.bufs.push_back(d.refit_lbox);
     HIP_OK(hipEventCreate(&d.refit_ev0));
@@ -196,16 +290,9 @@ int prepare(const Scene& s, DeviceState& d) {
 
 inline dim3 blocks(size_t n) { return dim3((unsigned)((n + kRefitWG - 1) / kRefitWG)); }
 
-// Enqueue on `stream`: scatter nv vertices (and nn normals) from packed device arrays into
-// mesh m's slices, then the leaf kernel and the node kernels.
-int enqueue(DeviceState& d, int m, const float* d_verts, uint32_t nv, const float* d_normals, uint32_t nn,
-            hipStream_t stream) {
-    if (nv)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
-                           d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
-    if (d_normals && nn)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
-                           (float4*)nullptr, d_normals, nn, 0.f);
+// Enqueue on `stream`: the leaf kernel over the world packets and the node kernels, deepest
+// height first.
+int enqueue_tree(DeviceState& d, hipStream_t stream) {
     const uint32_t n_lanes = 4u * d.n_world_leaves;
     if (n_lanes)
         hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves, n_lanes, d.prims,
@@ -221,13 +308,48 @@ int enqueue(DeviceState& d, int m, const float* d_verts, uint32_t nv, const floa
     return MRT_OK;
 }
 
+// Enqueue on `stream`: scatter nv vertices (and nn normals) from packed device arrays into
+// mesh m's slices, then the tree.
+int enqueue(DeviceState& d, int m, const float* d_verts, uint32_t nv, const float* d_normals, uint32_t nn,
+            hipStream_t stream) {
+    if (nv)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
+                           d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
+    if (d_normals && nn)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
+                           (float4*)nullptr, d_normals, nn, 0.f);
+    return enqueue_tree(d, stream);
+}
+
+// Enqueue on `stream`: n matrices (device, row-major 4x4 each) for the instances d_ids[0 .. n)
+// (nullptr: first .. first + n - 1), then the tree.  The ids are in [0, d.n_insts).
+int enqueue_instances(DeviceState& d, const float* d_m16s, const int32_t* d_ids, int32_t first, uint32_t n,
+                      hipStream_t stream) {
+    if (n)
+        hipLaunchKernelGGL(refit_instance_kernel, blocks(n), dim3(kRefitWG), 0, stream, d.insts, d.refit_inst_m,
+                           d.refit_fixed, (const QNode*)d.nodes, (const uint16_t*)d.tables, d_m16s, d_ids, first, n);
+    return enqueue_tree(d, stream);
+}
+
+// the synchronous entries' staging buffer on replica d holds `need` floats
+int stage_reserve(DeviceState& d, size_t need) {
+    if (need <= d.refit_stage_cap) return MRT_OK;
+    if (d.refit_stage) (void)hipFree(d.refit_stage);
+    d.refit_stage = nullptr;
+    d.refit_stage_cap = 0;
+    HIP_OK(hipMalloc((void**)&d.refit_stage, need * sizeof(float)));
+    d.refit_stage_cap = need;
+    return MRT_OK;
+}
+
 }  // namespace
 
 // The host copy from replica s.dev (or the first one): node boxes and leaf triangles in
-// canonical numbers and layout, the vertices and normals of the meshes an async update left
-// on the device, and from them the binning boxes of every replica.
+// canonical numbers and layout, the vertices and normals of the meshes and the matrices and
+// boxes of the instances an async update left on the device, and from them the binning boxes
+// of every replica.
 int sync_host(Scene& s, bool meshes_only) {
-    if (meshes_only ? s.host_mesh_stale.empty() : !s.host_stale()) return MRT_OK;
+    if (meshes_only ? s.host_mesh_stale.empty() && !s.host_inst_stale : !s.host_stale()) return MRT_OK;
     DeviceState* d = s.dev ? s.dev : (s.devs.empty() ? nullptr : s.devs[0]);
     if (!d) { set_error("refit: the device copy that is ahead of the host is gone"); return MRT_ERR_INVALID; }
     int cur = -1;
@@ -254,6 +376,27 @@ int sync_host(Scene& s, bool meshes_only) {
         for (size_t i = 0; i < M.normals.size(); i++) M.normals[i] = mk(buf[i].x, buf[i].y, buf[i].z);
     }
     s.host_mesh_stale.clear();
+    if (s.host_inst_stale && d->refit_ready && d->n_insts == (int)s.instances.size()) {
+        // m_transform from the replica's copy, m_inverse and rows 0-2 of m_invTranspose from
+        // DevInstance (row 3 of the transpose is column 3 of the inverse), the box from the fixed boxes
+        const size_t ni = s.instances.size();
+        std::vector<DevInstance> DI(ni);
+        std::vector<float> M(16 * ni);
+        std::vector<float4> FB(2 * ni);
+        HIP_OK(hipMemcpy(DI.data(), d->insts, ni * sizeof(DevInstance), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(M.data(), d->refit_inst_m, M.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(FB.data(), d->refit_fixed, FB.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < ni; i++) {
+            Instance& I = s.instances[i];
+            memcpy(I.m, &M[16 * i], sizeof I.m);
+            memcpy(I.inv, DI[i].inv, sizeof I.inv);
+            memcpy(I.inv_t, DI[i].inv_t, sizeof DI[i].inv_t);
+            for (int c = 0; c < 4; c++) I.inv_t[12 + c] = I.inv[4 * c + 3];
+            I.box[0] = FB[2 * i].x; I.box[1] = FB[2 * i].y; I.box[2] = FB[2 * i].z;
+            I.box[3] = FB[2 * i + 1].x; I.box[4] = FB[2 * i + 1].y; I.box[5] = FB[2 * i + 1].z;
+        }
+    }
+    s.host_inst_stale = false;
     if (!meshes_only) s.host_bvh_stale = false;
     if (!meshes_only && !s.nodes.empty())
         for (DeviceState* r : s.devs) root_box(s.nodes[0], r->bb_lo, r->bb_hi);
@@ -290,14 +433,7 @@ int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts, const floa
         HIP_OK(hipSetDevice(d->device));
         HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
         if ((rc = prepare(S, *d))) return rc;
-        const size_t need = ((size_t)nv + nn) * 3;
-        if (need > d->refit_stage_cap) {
-            if (d->refit_stage) (void)hipFree(d->refit_stage);
-            d->refit_stage = nullptr;
-            d->refit_stage_cap = 0;
-            HIP_OK(hipMalloc((void**)&d->refit_stage, need * sizeof(float)));
-            d->refit_stage_cap = need;
-        }
+        if ((rc = stage_reserve(*d, ((size_t)nv + nn) * 3))) return rc;
         if (nv) HIP_OK(hipMemcpy(d->refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
         if (nn) HIP_OK(hipMemcpy(d->refit_stage + (size_t)nv * 3, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
         if (!M.tidx.empty() && d->tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
@@ -344,6 +480,70 @@ int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts, co
     S.host_bvh_stale = true;
     if (std::find(S.host_mesh_stale.begin(), S.host_mesh_stale.end(), mesh) == S.host_mesh_stale.end())
         S.host_mesh_stale.push_back(mesh);
+    return MRT_OK;
+}
+
+int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n, const float* m16s, float* refit_ms) {
+    if (refit_ms) *refit_ms = 0.f;
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    if (!m16s) { set_error("update_instances: null matrices"); return MRT_ERR_INVALID; }
+    std::vector<Instance> NI;   // arguments first: no device call and no change before
+    int rc = instances_check(S, ids, 0, n, m16s, &NI);
+    if (rc) return rc;
+    if (n == 0) return MRT_OK;
+    auto apply = [&] {
+        for (int32_t k = 0; k < n; k++) S.instances[(size_t)(ids ? ids[k] : k)] = NI[(size_t)k];
+    };
+    const bool on_device = !S.dev_dirty && !S.devs.empty();
+    if (!on_device) {   // built, not uploaded (or a re-upload is due anyway): the host refit reads Instance::box
+        if ((rc = sync_host(S))) return rc;
+        apply();
+        refit_host(S);
+        return MRT_OK;
+    }
+    if ((rc = sync_host(S, true))) return rc;   // the host instances are current from here (the hierarchy stays on the device)
+    DeviceState* cur = S.dev ? S.dev : S.devs[0];
+    for (DeviceState* d : S.devs) {
+        HIP_OK(hipSetDevice(d->device));
+        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
+        if ((rc = prepare(S, *d))) return rc;
+        if ((rc = stage_reserve(*d, (size_t)n * 17))) return rc;   // n matrices, then n ids
+        int32_t* d_ids = ids ? (int32_t*)(d->refit_stage + (size_t)n * 16) : nullptr;
+        HIP_OK(hipMemcpy(d->refit_stage, m16s, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice));
+        if (ids) HIP_OK(hipMemcpy(d_ids, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
+        if ((rc = enqueue_instances(*d, d->refit_stage, d_ids, 0, (uint32_t)n, nullptr))) return rc;
+        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
+        HIP_OK(hipEventSynchronize(d->refit_ev1));
+        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
+        QNode root;   // the binning box follows the refitted root
+        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
+        root_box(root, d->bb_lo, d->bb_hi);
+    }
+    apply();
+    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
+    HIP_OK(hipSetDevice(cur->device));
+    return MRT_OK;
+}
+
+int mrt_scene_update_instances_async(mrt_scene* s, int32_t first, int32_t n, const float* d_m16s, void* stream) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    if (!d_m16s) { set_error("update_instances: null matrices"); return MRT_ERR_INVALID; }
+    int rc = instances_check(S, nullptr, first, n, nullptr, nullptr);   // the range: the kernel trusts its ids
+    if (rc) return rc;
+    if (n == 0) return MRT_OK;
+    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
+        set_error("update_instances_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
+        return MRT_ERR_INVALID;
+    }
+    DeviceState& d = *S.dev;
+    HIP_OK(hipSetDevice(d.device));
+    if ((rc = prepare(S, d))) return rc;
+    if ((rc = enqueue_instances(d, d_m16s, nullptr, first, (uint32_t)n, (hipStream_t)stream))) return rc;
+    S.host_bvh_stale = true;
+    S.host_inst_stale = true;
     return MRT_OK;
 }
 

@@ -116,9 +116,12 @@ struct Scene {
     // node boxes and leaf triangles are then ahead of nodes / leaves (host_bvh_stale), and
     // after the async form the vertices and normals of host_mesh_stale's meshes too.
     // sync_host (mrt_refit.hip) reads them back before anything reads the host copy.
+    // After mrt_scene_update_instances_async the matrices, inverses and boxes of `instances`
+    // are behind the replica's too (host_inst_stale).
     bool host_bvh_stale = false;
     std::vector<int32_t> host_mesh_stale;
-    bool host_stale() const { return host_bvh_stale || !host_mesh_stale.empty(); }
+    bool host_inst_stale = false;
+    bool host_stale() const { return host_bvh_stale || !host_mesh_stale.empty() || host_inst_stale; }
 
     // device replicas (one per HIP device used, mrt_render_opts.devices); `dev` is
     // the one the last call used.  dev_dirty: the host scene changed, every
@@ -138,6 +141,9 @@ int load_obj(const char* path, const float* ctm16, Mesh& out, std::string& err);
 int build_qbvh(Scene& s, std::string& err);
 int make_blas(Scene& s, const int32_t* meshes, int n_meshes, std::string& err);
 int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err);
+// m, inv, inv_t and box of I from the row-major 4x4 m16 and the root of BLAS I.blas
+// (add_instance's arithmetic; mrt_scene_update_instances uses it for a built scene)
+void instance_set_matrix(const Scene& s, Instance& I, const float* m16);
 // The refit on the host: the world leaf triangles from the meshes' vertices (make_leaf),
 // then every box bottom-up, topology kept (the arithmetic of mrt_refit.hip's kernels).
 void refit_host(Scene& s);
@@ -146,8 +152,14 @@ void refit_host(Scene& s);
 bool fixed_lane_box(const Scene& s, int32_t o, float box[6]);
 // mrt_refit.hip: bring a stale host copy up to date from the device (synchronises); a
 // no-op when nothing is stale
-// (meshes_only: the vertices and normals an async update left there, not the hierarchy)
+// (meshes_only: the vertices and normals, and the instances, an async update left there, not
+// the hierarchy)
 int sync_host(Scene& s, bool meshes_only = false);
+// host_api.cpp: the argument checks of mrt_scene_update_instances (m16s == nullptr: the async
+// form, whose matrices are on the device; ids == nullptr: first .. first + n - 1).  out: the
+// instances of the batch with their new matrices, inverses and boxes, nothing changed yet
+int instances_check(const Scene& s, const int32_t* ids, int32_t first, int32_t n, const float* m16s,
+                    std::vector<Instance>* out);
 // host_api.cpp: the argument checks of mrt_scene_update_mesh (verts == nullptr: the async
 // form, whose arrays are on the device), and the new arrays into the host mesh
 int refit_check(const Scene& s, int mesh, const float* verts, const float* normals);

@@ -742,6 +742,64 @@ class Scene:
                                       C.byref(ms)), "updateMesh")
         return float(ms.value)
 
+    def updateInstances(self, matrices, ids=None, first=0, stream=None):
+        """New m_transform matrices for ProxyObject instances of the built scene
+        (ProxyMatrix::set, then a refit where the reference rebuilds; mrt_scene_update_instances):
+        inverse, inverse transpose and box per instance as addObject computes them, the BLAS and
+        every hit id untouched, the world hierarchy refitted in place.
+        numpy input ((n, 4, 4) or (n, 16)) or a sequence of Matrix4x4 goes through the
+        synchronous entry for the instances `ids` (None: first .. first + n - 1) and returns the
+        device time of the kernels in ms (0.0 for a scene not yet uploaded: the host refits).
+        A contiguous float32 torch tensor (n, 4, 4) on the scene's device goes through
+        mrt_scene_update_instances_async on `stream` (a torch stream; default: the current
+        one) for the range first .. first + n - 1, without a host copy or a synchronisation,
+        and returns None; `ids` must be None and the matrices finite and invertible (they are
+        not checked).  The ProxyObjects given to addObject keep the matrices they had."""
+        L = lib()
+        if hasattr(matrices, "data_ptr"):
+            import torch
+            m = matrices
+            if not (m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and m.device.index == self.device
+                    and m.dim() == 3 and tuple(m.shape[1:]) == (4, 4)):
+                raise MRTError("updateInstances: the tensor must be contiguous float32 (n, 4, 4) on the scene's device")
+            if ids is not None:
+                raise MRTError("updateInstances: device tensors take a range (first), not ids")
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            st = (stream if stream is not None else torch.cuda.current_stream(m.device)).cuda_stream
+            check(L.mrt_scene_update_instances_async(self.handle, int(first), int(m.shape[0]), m.data_ptr(), st),
+                  "updateInstances")
+            return None
+        if not isinstance(matrices, np.ndarray):
+            matrices = [x.m if isinstance(x, Matrix4x4) else x for x in matrices]
+        m = np.ascontiguousarray(matrices, np.float32)
+        if m.size % 16 or (m.ndim == 3 and m.shape[1:] != (4, 4)):
+            raise MRTError("updateInstances: matrices must be (n, 4, 4)")
+        n = m.size // 16
+        if ids is None:
+            idv = np.arange(int(first), int(first) + n, dtype=np.int32) if first else None
+        else:
+            idv = np.ascontiguousarray(ids, np.int32).reshape(-1)
+            if first or len(idv) != n:
+                raise MRTError("updateInstances: one id per matrix, and no `first` beside ids")
+        ms = C.c_float(0.0)
+        check(L.mrt_scene_update_instances(self.handle, idv.ctypes.data if idv is not None else None, n, m.ctypes.data,
+                                           C.byref(ms)), "updateInstances")
+        return float(ms.value)
+
+    def instance_count(self):
+        return check(lib().mrt_scene_instance_count(self.handle), "instance_count")
+
+    def instance_info(self, i: int):
+        """What instance i holds now (mrt_scene_instance_info): blas, m, inv, inv_t ((4, 4)
+        float32 each) and box ((2, 3): min, max).  Reads the device back after an async update."""
+        blas = C.c_int32()
+        m, inv, inv_t = (np.zeros((4, 4), np.float32) for _ in range(3))
+        box = np.zeros((2, 3), np.float32)
+        fp = C.POINTER(C.c_float)
+        check(lib().mrt_scene_instance_info(self.handle, int(i), C.byref(blas), m.ctypes.data_as(fp), inv.ctypes.data_as(fp),
+                                            inv_t.ctypes.data_as(fp), box.ctypes.data_as(fp)), "instance_info")
+        return dict(blas=blas.value, m=m, inv=inv, inv_t=inv_t, box=box)
+
     # -- rendering (src/Scene.cpp:85-217)
     def raytraceImage(self, cam: Camera, img: Image, count_visits=False, want_hits=False, seed=0, devices=None):
         """devices: HIP device ordinals to deal the 32x32 buckets over (bucket b ->
