@@ -371,7 +371,8 @@ int mrt_scene_upload(mrt_scene* s, int device);
  *  - a mesh with texture coordinates gets its tangent frames recomputed on the host
  *    (TriangleMesh::preCalc) and uploaded.
  * After an update of an uploaded scene mrt_scene_bvh_export returns the arrays the
- * device holds, read back and converted to the canonical layout. */
+ * device holds, read back and converted to the canonical layout.
+ * mrt_scene_deform_mesh (below) takes the two kinds of mesh refused here. */
 int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts,
                           const float* normals, float* refit_ms);
 /* The same with device pointers, enqueued on `stream`, never synchronising (the first
@@ -402,8 +403,8 @@ int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts,
  *    names its position in the batch); MRT_ERR_NOT_BUILT for an unbuilt scene.
  *  - a scene that is built but not uploaded (or due for a re-upload) is updated and
  *    refitted on the host: the same arithmetic.
- * Out of scope: new vertices for a mesh of a BLAS (a BLAS refit, then this call),
- * motion-blurred meshes, adding or removing instances, changing an instance's BLAS, any
+ * New vertices for a mesh of a BLAS or a motion-blurred mesh: mrt_scene_deform_mesh.
+ * Out of scope: adding or removing instances, changing an instance's BLAS, any
  * rebuild heuristic (tree quality degrades as instances travel; mrt_scene_build_bvh on a
  * new scene remains the remedy), and the shim. */
 int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n,
@@ -423,6 +424,44 @@ int mrt_scene_update_instances_async(mrt_scene* s, int32_t first, int32_t n,
 int mrt_scene_instance_count(const mrt_scene* s);
 int mrt_scene_instance_info(const mrt_scene* s, int32_t inst, int32_t* blas, float m16[16],
                             float inv16[16], float inv_t16[16], float box6[6]);
+
+/* ---- any mesh deformed in place: same counts, same triangles, new positions (DESIGN.md
+ * "Deform").  verts (nv*3) and, when not NULL, normals (nn*3) replace the mesh's own; the
+ * kind of mesh decides the rest:
+ *  - a plain world mesh: exactly mrt_scene_update_mesh (verts2 must be NULL).
+ *  - a mesh of a BLAS (verts2 must be NULL: a BLAS mesh's motion vertices are inert, only
+ *    world meshes make MBObjects): that BLAS is refitted in place (leaf triangles A, B-A,
+ *    C-A, packet boxes merged in lane order from the empty box, node boxes per height,
+ *    deepest first: mrt_scene_blas_export states the result), then the
+ *    ProxyObject::getAABB box of every instance of that BLAS is recomputed from the new
+ *    root and the instance's current m_transform (mrt_scene_add_instance's arithmetic;
+ *    m_inverse and m_invTranspose stay), then the world hierarchy is refitted.  Hit ids,
+ *    child words, leaf prims, every other BLAS and the boxes of its instances stay.
+ *  - a motion-blurred world mesh (mrt_scene_set_mesh_motion): verts2 (nv*3, time 1) is
+ *    required beside verts (time 0); each of its MBObject boxes becomes the union of the
+ *    triangle's box at both times (later update_mesh / update_instances calls keep it),
+ *    then the world hierarchy is refitted.
+ * Everything is checked before any device call and before any change.  MRT_ERR_INVALID
+ * for a null scene or null verts, a bad mesh id, verts2 given for a mesh without motion
+ * vertices or missing for one with them, a vertex, motion vertex or normal that is not
+ * finite (the first bad index is in mrt_last_error) and a hierarchy from
+ * mrt_scene_bvh_import; MRT_ERR_NOT_BUILT for an unbuilt scene.  A scene that is built but
+ * not uploaded (or due for a re-upload) is deformed on the host: the same arithmetic.  A
+ * mesh with texture coordinates gets its tangent frames recomputed on the host.
+ * *refit_ms (nullable): device time of the kernels on the current device.
+ * Out of scope: motion-blurred meshes inside a BLAS, topology changes, any rebuild
+ * heuristic, and the shim. */
+int mrt_scene_deform_mesh(mrt_scene* s, int mesh, const float* verts, const float* verts2,
+                          const float* normals, float* refit_ms);
+/* The same with device pointers, enqueued on `stream`, never synchronising (the first refit
+ * of a replica allocates and uploads its schedule).  Only the id and the kind of mesh are
+ * checked; the arrays must be finite.  It needs the scene uploaded to exactly one device
+ * and refuses a mesh with texture coordinates.  The host copy is left stale:
+ * mrt_scene_bvh_export, mrt_scene_blas_export, mrt_scene_mesh_export,
+ * mrt_scene_instance_info, mrt_scene_add_instance, mrt_scene_update_instances, a host refit,
+ * a re-upload and an upload to a second device first read the device state back. */
+int mrt_scene_deform_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_verts2,
+                                const float* d_normals, void* stream);
 
 /* ---- frame entry: Scene::raytraceImage(Camera*, Image*) (src/Scene.cpp:85-217).
  * Synchronous, host buffers: rgb (W*H*3 floats, before Map) and rgb8 (W*H*3,

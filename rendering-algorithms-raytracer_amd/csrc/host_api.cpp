@@ -104,6 +104,48 @@ void refit_set_mesh(Mesh& m, const float* verts, const float* normals) {
     mesh_tangents(m);   // TriangleMesh::preCalc of a texture-mapped mesh
 }
 
+// mrt_scene_deform_mesh / _async (mrt_refit.hip): which scenes, meshes and arrays it takes
+int deform_check(const Scene& S, int mesh, const float* verts, const float* verts2, bool has_verts2, const float* normals,
+                 int* kind) {
+    if (!S.built) { set_error("deform_mesh: scene not built"); return MRT_ERR_NOT_BUILT; }
+    if (mesh < 0 || mesh >= (int)S.meshes.size()) { set_error("deform_mesh: bad mesh id"); return MRT_ERR_INVALID; }
+    const Mesh& m = S.meshes[(size_t)mesh];
+    const bool in_blas = S.mesh_blas[(size_t)mesh] >= 0;
+    if (in_blas && has_verts2) {
+        set_error("deform_mesh: motion vertices given for a mesh of a BLAS (a BLAS mesh's motion vertices are inert: only world meshes make MBObjects)");
+        return MRT_ERR_INVALID;
+    }
+    if (!in_blas && m.verts2.empty() && has_verts2) {
+        set_error("deform_mesh: motion vertices given for a mesh without them (mrt_scene_set_mesh_motion)");
+        return MRT_ERR_INVALID;
+    }
+    if (!in_blas && !m.verts2.empty() && !has_verts2) {
+        set_error("deform_mesh: the mesh has motion vertices (mrt_scene_set_mesh_motion): give both sets, an MBObject's box needs them");
+        return MRT_ERR_INVALID;
+    }
+    if (S.imported) {
+        set_error("deform_mesh: the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
+        return MRT_ERR_INVALID;
+    }
+    auto finite = [&](const float* p, size_t n, const char* what) {
+        for (size_t i = 0; i < 3 * n; i++)
+            if (!std::isfinite(p[i])) {
+                set_error(std::string("deform_mesh: ") + what + " " + std::to_string(i / 3) + " is not finite");
+                return false;
+            }
+        return true;
+    };
+    if (verts && !finite(verts, m.verts.size(), "vertex")) return MRT_ERR_INVALID;
+    if (verts && verts2 && !finite(verts2, m.verts.size(), "motion vertex")) return MRT_ERR_INVALID;
+    if (verts && normals && !finite(normals, m.normals.size(), "normal")) return MRT_ERR_INVALID;
+    *kind = in_blas ? kDeformBlas : has_verts2 ? kDeformMotion : kDeformWorld;
+    return MRT_OK;
+}
+
+void deform_set_motion(Mesh& m, const float* verts2) {
+    for (size_t i = 0; i < m.verts2.size(); i++) m.verts2[i] = mk(verts2[3 * i], verts2[3 * i + 1], verts2[3 * i + 2]);
+}
+
 // mrt_scene_update_instances / _async (mrt_refit.hip): which scenes, ids and matrices it takes
 int instances_check(const Scene& S, const int32_t* ids, int32_t first, int32_t n, const float* m16s,
                     std::vector<Instance>* out) {
@@ -246,6 +288,7 @@ int mrt_scene_make_blas(mrt_scene* s, const int32_t* meshes, int32_t n_meshes) {
 
 int mrt_scene_add_instance(mrt_scene* s, int32_t blas, const float* m16) {
     if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (const int rc = sync_host(s->impl)) return rc;   // the box comes from the BLAS root: a device deform may be ahead
     std::string err;
     const int rc = add_instance(s->impl, blas, m16, err);
     if (rc < 0) set_error(err);
@@ -271,6 +314,8 @@ int mrt_scene_blas_export(const mrt_scene* s, int32_t blas, float* node_boxes, i
         set_error("bad BLAS id / argument");
         return MRT_ERR_INVALID;
     }
+    // after a device deform of one of its meshes: the arrays the device holds, read back
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
     const Blas& B = s->impl.blas[blas];
     for (size_t i = 0; i < B.nodes.size(); i++) {
         memcpy(node_boxes + 24 * i, B.nodes[i].box, 24 * sizeof(float));
@@ -499,6 +544,7 @@ int mrt_scene_mesh_set_texcoords(mrt_scene* s, int mesh, const float* uv, int32_
 
 int mrt_scene_set_mesh_motion(mrt_scene* s, int mesh, const float* verts2) {
     if (!s || mesh < 0 || mesh >= (int)s->impl.meshes.size() || !verts2) { set_error("bad mesh id"); return MRT_ERR_INVALID; }
+    if (const int rc = sync_host(s->impl)) return rc;   // an async deform's vertex sets come back first, not over these
     Mesh& m = s->impl.meshes[mesh];
     m.verts2.resize(m.verts.size());
     for (size_t i = 0; i < m.verts.size(); i++) m.verts2[i] = v3{verts2[3*i], verts2[3*i+1], verts2[3*i+2]};

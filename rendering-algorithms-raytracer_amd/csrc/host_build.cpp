@@ -1215,7 +1215,13 @@ void instance_set_matrix(const Scene& s, Instance& I, const float* m16) {
     memcpy(I.m, M.m, sizeof I.m);
     memcpy(I.inv, inv.m, sizeof I.inv);
     memcpy(I.inv_t, inv_t.m, sizeof I.inv_t);
-    const QNode& r = s.blas[blas].nodes[0];
+    instance_box(s.blas[blas].nodes[0], m16, I.box);
+}
+
+// ProxyObject::getAABB alone (mrt_scene_deform_mesh: the root moved, the matrix did not)
+void instance_box(const QNode& r, const float* m16, float box[6]) {
+    Mat4 M;
+    memcpy(M.m, m16, sizeof M.m);
     Box t = empty_box();
     for (int k = 0; k < 4; k++)
         t = merge(t, Box{{r.box[0 + k], r.box[4 + k], r.box[8 + k]}, {r.box[12 + k], r.box[16 + k], r.box[20 + k]}});
@@ -1228,8 +1234,8 @@ void instance_set_matrix(const Scene& s, Instance& I, const float* m16) {
         nb = merge(nb, Box{{q.x, q.y, q.z}, {q.x, q.y, q.z}});
     }
     for (int k = 0; k < 3; k++) {
-        I.box[k] = nb.mn[k];
-        I.box[3 + k] = nb.mx[k];
+        box[k] = nb.mn[k];
+        box[3 + k] = nb.mx[k];
     }
 }
 
@@ -1276,6 +1282,38 @@ bool fixed_lane_box(const Scene& s, int32_t o, float box[6]) {
 // merge of that child's used slots in slot order; empty slots keep their zero box.  Every
 // child of a built hierarchy has a larger number than its parent (qbuild), so one pass from
 // the last node to the first is bottom-up.
+namespace {
+// every box of `nodes` bottom-up from the packet boxes
+void refit_nodes(std::vector<QNode>& nodes, const std::vector<Box>& lbox) {
+    for (size_t qi = nodes.size(); qi-- > 0;) {
+        QNode& q = nodes[qi];
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = q.child[k];
+            if (c == kEmptySlot) continue;
+            Box b;
+            if (c < 0) b = lbox[(size_t)~c];
+            else {
+                const QNode& ch = nodes[(size_t)c];
+                b = empty_box();
+                for (int j = 0; j < 4; j++)
+                    if (ch.child[j] != kEmptySlot) b = merge(b, slot_box(ch, j));
+            }
+            q.box[0 + k] = b.mn[0]; q.box[4 + k] = b.mn[1]; q.box[8 + k] = b.mn[2];
+            q.box[12 + k] = b.mx[0]; q.box[16 + k] = b.mx[1]; q.box[20 + k] = b.mx[2];
+        }
+    }
+}
+// lane i of packet L from triangle `tri` of mesh m (make_leaf); its box
+Box refit_lane(QLeaf& L, int i, const Mesh& m, int32_t tri) {
+    const uint32_t* f = &m.vidx[3 * (size_t)tri];
+    const v3 A = m.verts[f[0]], B = m.verts[f[1]], C = m.verts[f[2]];
+    L.t[0 + i] = A.x; L.t[4 + i] = A.y; L.t[8 + i] = A.z;
+    L.t[12 + i] = B.x - A.x; L.t[16 + i] = B.y - A.y; L.t[20 + i] = B.z - A.z;
+    L.t[24 + i] = C.x - A.x; L.t[28 + i] = C.y - A.y; L.t[32 + i] = C.z - A.z;
+    return verts_box3(A, B, C);
+}
+}  // namespace
+
 void refit_host(Scene& s) {
     std::vector<Box> lbox(s.leaves.size());
     for (size_t li = 0; li < s.leaves.size(); li++) {
@@ -1285,37 +1323,33 @@ void refit_host(Scene& s) {
             const int32_t o = L.prim[i];
             if (o < 0) continue;
             float fb[6];
-            if (fixed_lane_box(s, o, fb)) {   // checkOut lanes: no triangle data, the build's box
+            if (fixed_lane_box(s, o, fb)) {   // checkOut lanes: no triangle data, the box of the object now
                 b = merge(b, Box{{fb[0], fb[1], fb[2]}, {fb[3], fb[4], fb[5]}});
                 continue;
             }
-            const Mesh& m = s.meshes[(size_t)s.obj_mesh[(size_t)o]];
-            const uint32_t* f = &m.vidx[3 * (size_t)s.obj_tri[(size_t)o]];
-            const v3 A = m.verts[f[0]], B = m.verts[f[1]], C = m.verts[f[2]];
-            L.t[0 + i] = A.x; L.t[4 + i] = A.y; L.t[8 + i] = A.z;
-            L.t[12 + i] = B.x - A.x; L.t[16 + i] = B.y - A.y; L.t[20 + i] = B.z - A.z;
-            L.t[24 + i] = C.x - A.x; L.t[28 + i] = C.y - A.y; L.t[32 + i] = C.z - A.z;
-            b = merge(b, verts_box3(A, B, C));
+            b = merge(b, refit_lane(L, i, s.meshes[(size_t)s.obj_mesh[(size_t)o]], s.obj_tri[(size_t)o]));
         }
         lbox[li] = b;
     }
-    for (size_t qi = s.nodes.size(); qi-- > 0;) {
-        QNode& q = s.nodes[qi];
-        for (int k = 0; k < 4; k++) {
-            const int32_t c = q.child[k];
-            if (c == kEmptySlot) continue;
-            Box b;
-            if (c < 0) b = lbox[(size_t)~c];
-            else {
-                const QNode& ch = s.nodes[(size_t)c];
-                b = empty_box();
-                for (int j = 0; j < 4; j++)
-                    if (ch.child[j] != kEmptySlot) b = merge(b, slot_box(ch, j));
-            }
-            q.box[0 + k] = b.mn[0]; q.box[4 + k] = b.mn[1]; q.box[8 + k] = b.mn[2];
-            q.box[12 + k] = b.mx[0]; q.box[16 + k] = b.mx[1]; q.box[20 + k] = b.mx[2];
+    refit_nodes(s.nodes, lbox);
+}
+
+void refit_blas_host(Scene& s, int32_t bi) {
+    Blas& B = s.blas[(size_t)bi];
+    std::vector<Box> lbox(B.leaves.size());
+    for (size_t li = 0; li < B.leaves.size(); li++) {
+        QLeaf& L = B.leaves[li];
+        Box b = empty_box();
+        for (int i = 0; i < 4; i++) {
+            const int32_t o = L.prim[i];
+            if (o < 0) continue;
+            b = merge(b, refit_lane(L, i, s.meshes[(size_t)B.obj_mesh[(size_t)o]], B.obj_tri[(size_t)o]));
         }
+        lbox[li] = b;
     }
+    refit_nodes(B.nodes, lbox);
+    for (Instance& I : s.instances)
+        if (I.blas == bi) instance_box(B.nodes[0], I.m, I.box);
 }
 
 }  // namespace mrt

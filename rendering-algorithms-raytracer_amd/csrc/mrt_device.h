@@ -221,13 +221,28 @@ struct DeviceState {
     bool refit_ready = false;
     int32_t* refit_order = nullptr;       // world device node numbers sorted by height (one of bufs)
     std::vector<uint32_t> refit_off;      //   height h holds refit_order[refit_off[h] .. refit_off[h + 1])
-    float4* refit_lbox = nullptr;         // per world packet: box min xyz, max xyz (2 float4; one of bufs)
+    float4* refit_lbox = nullptr;         // per packet, world then BLASes, by device packet number: box min xyz, max xyz (2 float4; one of bufs)
     float4* refit_fixed = nullptr;        // ProxyObject lanes' boxes by instance, then MBObject lanes' (2 float4 each)
     int32_t* refit_mbslot = nullptr;      //   per world prim: its MBObject box after the instances', -1 = none
     float* refit_inst_m = nullptr;        // per instance: m_transform, 16 floats (refit_instance_kernel keeps it current; one of bufs)
     float* refit_stage = nullptr;         // the synchronous entry's packed vertices / normals on the device
     size_t refit_stage_cap = 0;           //   floats
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
+    // mrt_scene_deform_mesh: where each BLAS lies in nodes / leaves / prims (the upload; BLAS
+    // nodes are not permuted, their child words hold device node and packet numbers), and the
+    // schedule the first refit makes: its nodes by height and the ids of its instances
+    struct BlasRange {
+        uint32_t node_base = 0, n_nodes = 0, leaf_base = 0, n_leaves = 0;   // node_base is the root
+        int32_t shade_base = 0;                                             // PrimShade of its object 0
+        std::vector<uint32_t> off;         // height h holds refit_blas_order[order_at + off[h] .. order_at + off[h + 1])
+        uint32_t order_at = 0;
+        uint32_t inst_at = 0, n_inst = 0;  // refit_blas_insts[inst_at .. inst_at + n_inst): its instances, ascending
+    };
+    std::vector<BlasRange> blas;
+    uint32_t n_leaves_all = 0;             // packets of the world and every BLAS (refit_lbox holds them all)
+    int32_t* refit_blas_order = nullptr;   // device node numbers of every BLAS, each sorted by height (one of bufs)
+    int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS (one of bufs)
+    std::vector<int32_t> mesh_prim0;       // per mesh: its first world prim (its triangles follow in order), -1 = none
     int cus = 0;
     bool point_only = false;
     bool dome = false;           // a dome light (incoherent shadow rays)

@@ -7,6 +7,10 @@
 // mrt_scene_update_instances: new matrices for ProxyObject instances; one kernel restates
 // add_instance's arithmetic per instance (inverse, inverse transpose, box), then the same
 // leaf and node kernels.
+// mrt_scene_deform_mesh: new vertices for any mesh.  A mesh of a BLAS: the same leaf and node
+// kernels over that BLAS's range, one kernel that recomputes the box of each of its instances
+// from the refitted root, then the world tree.  A motion-blurred world mesh: both vertex sets,
+// one kernel that recomputes the union box of each of its MBObject lanes, then the world tree.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -189,6 +193,14 @@ __device__ DBox d_instance_box(const float (&m)[4][4], const QNode& r, const uin
     return nb;
 }
 
+// instance i's box from its matrix and its BLAS root, into the fixed boxes the leaf kernel reads
+__device__ __forceinline__ void d_fix_instance_box(float4* __restrict__ fixed, size_t i, const float (&m)[4][4],
+                                                   const QNode& root, const uint16_t* __restrict__ rcpT) {
+    const DBox b = d_instance_box(m, root, rcpT);
+    fixed[2 * i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
+    fixed[2 * i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+}
+
 // ProxyMatrix::set for n instances, one lane each: lane g takes the row-major 4x4 at
 // m16s + 16 g for instance ids[g] (ids == nullptr: first + g; the host checked the ids) and
 // writes its inverse and inverse transpose into insts, the matrix into inst_m and its box
@@ -214,9 +226,53 @@ __global__ __launch_bounds__(kRefitWG) void refit_instance_kernel(DevInstance* _
             if (r < 3) I.inv_t[4 * r + c] = inv[c][r];
             inst_m[i * 16 + 4 * r + c] = m[r][c];
         }
-    const DBox b = d_instance_box(m, nodes[I.root], rcpT);
-    fixed[2 * i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-    fixed[2 * i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+    d_fix_instance_box(fixed, i, m, nodes[I.root], rcpT);
+}
+
+// The box half alone for the n instances ids[0 .. n) of one BLAS whose root was just refitted:
+// lane g reads instance ids[g]'s m_transform from inst_m and writes its box.  inv, inv_t and
+// the matrix stay.  The RCPSS table comes from global memory, as in refit_instance_kernel.
+__global__ __launch_bounds__(kRefitWG) void refit_instance_box_kernel(float4* __restrict__ fixed,
+                                                                      const DevInstance* __restrict__ insts,
+                                                                      const float* __restrict__ inst_m,
+                                                                      const QNode* __restrict__ nodes,
+                                                                      const uint16_t* __restrict__ rcpT,
+                                                                      const int32_t* __restrict__ ids, uint32_t n) {
+    const uint32_t g = blockIdx.x * kRefitWG + threadIdx.x;
+    if (g >= n) return;
+    const size_t i = (size_t)ids[g];
+    float m[4][4];
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) m[r][c] = inst_m[i * 16 + 4 * r + c];
+    d_fix_instance_box(fixed, i, m, nodes[insts[i].root], rcpT);
+}
+
+// MBObject::getAABB for the n world prims first .. first + n - 1 (one motion-blurred mesh), one
+// lane each: box3 of the time-0 vertices merged with box3 of the time-1 vertices
+// (fixed_lane_box), into the prim's fixed box.
+__global__ __launch_bounds__(kRefitWG) void refit_motion_box_kernel(float4* __restrict__ fixed, int n_insts,
+                                                                    const int32_t* __restrict__ mbslot,
+                                                                    const uint8_t* __restrict__ pflags,
+                                                                    const PrimShade* __restrict__ prims,
+                                                                    const float4* __restrict__ verts,
+                                                                    const float4* __restrict__ verts2, uint32_t first,
+                                                                    uint32_t n) {
+    const uint32_t g = blockIdx.x * kRefitWG + threadIdx.x;
+    if (g >= n) return;
+    const size_t p = (size_t)first + g;
+    if (!(pflags[p] & 1u)) return;
+    const int32_t slot = mbslot[p];
+    if (slot < 0) return;
+    const PrimShade ps = prims[p];
+    auto box3 = [&](const float4* __restrict__ v) {
+        const float4 A = v[ps.v[0]], B = v[ps.v[1]], C = v[ps.v[2]];
+        return DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
+                    {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
+    };
+    const DBox b = d_merge(box3(verts), box3(verts2));
+    const size_t f = (size_t)n_insts + (size_t)slot;
+    fixed[2 * f] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
+    fixed[2 * f + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
 }
 
 template <typename T>
@@ -280,7 +336,46 @@ int prepare(const Scene& s, DeviceState& d) {
     std::vector<float> inst_m(16 * s.instances.size());   // m_transform: the device keeps inv / inv_t only
     for (size_t i = 0; i < s.instances.size(); i++) memcpy(&inst_m[16 * i], s.instances[i].m, 16 * sizeof(float));
     if ((rc = dev_array(d, d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float)))) return rc;
-    HIP_OK(hipMalloc((void**)&d.refit_lbox, std::max<size_t>(1, s.leaves.size()) * 2 * sizeof(float4)));
+    // each BLAS: its nodes by height in device numbers (node_base + canonical number: BLAS
+    // nodes are not permuted) and the ids of its instances; first prim of each world mesh
+    if (d.blas.size() != s.blas.size() || d.n_leaves_all < d.n_world_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    std::vector<int32_t> border, binsts;
+    for (size_t b = 0; b < s.blas.size(); b++) {
+        const std::vector<QNode>& BN = s.blas[b].nodes;
+        DeviceState::BlasRange& R = d.blas[b];
+        if (BN.size() != R.n_nodes || s.blas[b].leaves.size() != R.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+        std::vector<int32_t> bh(BN.size(), 0);
+        int32_t btop = 0;
+        for (size_t i = BN.size(); i-- > 0;) {
+            int32_t h = 0;
+            for (int k = 0; k < 4; k++) {
+                const int32_t c = BN[i].child[k];
+                if (c < 0) continue;
+                if ((size_t)c <= i || (size_t)c >= BN.size()) { set_error("refit: a BLAS hierarchy is not a tree in build order"); return MRT_ERR_INVALID; }
+                h = std::max(h, bh[(size_t)c] + 1);
+            }
+            bh[i] = h;
+            btop = std::max(btop, h);
+        }
+        R.off.assign((size_t)btop + 2, 0);
+        for (size_t i = 0; i < BN.size(); i++) R.off[(size_t)bh[i] + 1]++;
+        for (size_t h = 0; h + 1 < R.off.size(); h++) R.off[h + 1] += R.off[h];
+        R.order_at = (uint32_t)border.size();
+        border.resize(border.size() + BN.size());
+        std::vector<uint32_t> bat(R.off.begin(), R.off.end() - 1);
+        for (size_t i = 0; i < BN.size(); i++) border[R.order_at + bat[(size_t)bh[i]]++] = (int32_t)(R.node_base + i);
+        R.inst_at = (uint32_t)binsts.size();
+        for (size_t i = 0; i < s.instances.size(); i++)
+            if (s.instances[i].blas == (int32_t)b) binsts.push_back((int32_t)i);
+        R.n_inst = (uint32_t)binsts.size() - R.inst_at;
+    }
+    if ((rc = dev_array(d, d.refit_blas_order, border.data(), border.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_array(d, d.refit_blas_insts, binsts.data(), binsts.size() * sizeof(int32_t)))) return rc;
+    d.mesh_prim0.assign(s.meshes.size(), -1);
+    for (size_t o = s.obj_mesh.size(); o-- > 0;)
+        if (s.obj_mesh[o] >= 0) d.mesh_prim0[(size_t)s.obj_mesh[o]] = (int32_t)o;
+    // the packet boxes of the world and of every BLAS, by device packet number (the child words' own)
+    HIP_OK(hipMalloc((void**)&d.refit_lbox, std::max<size_t>(1, d.n_leaves_all) * 2 * sizeof(float4)));
     d.bufs.push_back(d.refit_lbox);
     HIP_OK(hipEventCreate(&d.refit_ev0));
     HIP_OK(hipEventCreate(&d.refit_ev1));
@@ -331,6 +426,55 @@ int enqueue_instances(DeviceState& d, const float* d_m16s, const int32_t* d_ids,
     return enqueue_tree(d, stream);
 }
 
+// Enqueue on `stream`: BLAS b refitted to the vertices the device holds now: the leaf kernel
+// over its packets (its PrimShade records start at shade_base; a BLAS has no fixed lanes), its
+// node kernels deepest height first, then the boxes of its instances.
+int enqueue_blas(DeviceState& d, int b, hipStream_t stream) {
+    const DeviceState::BlasRange& R = d.blas[(size_t)b];
+    const uint32_t n_lanes = 4u * R.n_leaves;
+    if (n_lanes)
+        hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves + R.leaf_base, n_lanes,
+                           (const PrimShade*)(d.prims + R.shade_base), (const float4*)d.verts, (const uint8_t*)nullptr,
+                           (const int32_t*)nullptr, (const float4*)d.refit_fixed, d.n_insts,
+                           d.refit_lbox + 2 * (size_t)R.leaf_base);
+    for (size_t h = 0; h + 1 < R.off.size(); h++) {
+        const uint32_t n = R.off[h + 1] - R.off[h];
+        if (!n) continue;
+        hipLaunchKernelGGL(refit_node_kernel, blocks((size_t)4 * n), dim3(kRefitWG), 0, stream, d.nodes,
+                           d.refit_blas_order + R.order_at + R.off[h], n, d.refit_lbox);
+    }
+    if (R.n_inst)
+        hipLaunchKernelGGL(refit_instance_box_kernel, blocks(R.n_inst), dim3(kRefitWG), 0, stream, d.refit_fixed,
+                           (const DevInstance*)d.insts, (const float*)d.refit_inst_m, (const QNode*)d.nodes,
+                           (const uint16_t*)d.tables, (const int32_t*)(d.refit_blas_insts + R.inst_at), R.n_inst);
+    return MRT_OK;
+}
+
+// Enqueue on `stream` for mesh m of `kind` (deform_check): the scatters, what the kind needs
+// between them and the world tree (blas: the mesh's BLAS), then the world tree.
+int enqueue_deform(DeviceState& d, int m, int kind, int blas, const float* d_verts, const float* d_verts2, uint32_t nv,
+                   const float* d_normals, uint32_t nn, uint32_t nt, hipStream_t stream) {
+    if (kind == kDeformWorld) return enqueue(d, m, d_verts, nv, d_normals, nn, stream);
+    const bool motion = kind == kDeformMotion && d.has_mb;
+    if (nv)   // a mesh of a BLAS is static: its time-1 copy follows, as in enqueue()
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
+                           kind == kDeformBlas && d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
+    if (nv && motion)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts2 + d.vbase[(size_t)m],
+                           (float4*)nullptr, d_verts2, nv, 1.f);
+    if (d_normals && nn)
+        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
+                           (float4*)nullptr, d_normals, nn, 0.f);
+    if (kind == kDeformBlas) {
+        if (const int rc = enqueue_blas(d, blas, stream)) return rc;
+    } else if (motion && nt && d.mesh_prim0[(size_t)m] >= 0) {
+        hipLaunchKernelGGL(refit_motion_box_kernel, blocks(nt), dim3(kRefitWG), 0, stream, d.refit_fixed, d.n_insts,
+                           (const int32_t*)d.refit_mbslot, (const uint8_t*)d.pflags, (const PrimShade*)d.prims,
+                           (const float4*)d.verts, (const float4*)d.verts2, (uint32_t)d.mesh_prim0[(size_t)m], nt);
+    }
+    return enqueue_tree(d, stream);
+}
+
 // the synchronous entries' staging buffer on replica d holds `need` floats
 int stage_reserve(DeviceState& d, size_t need) {
     if (need <= d.refit_stage_cap) return MRT_OK;
@@ -340,6 +484,14 @@ int stage_reserve(DeviceState& d, size_t need) {
     HIP_OK(hipMalloc((void**)&d.refit_stage, need * sizeof(float)));
     d.refit_stage_cap = need;
     return MRT_OK;
+}
+
+// after a device deform of a mesh of BLAS b: its host nodes and leaves, and the boxes of its
+// instances, are behind the replica's
+void mark_blas_stale(Scene& S, int32_t b) {
+    if (std::find(S.host_blas_stale.begin(), S.host_blas_stale.end(), b) == S.host_blas_stale.end())
+        S.host_blas_stale.push_back(b);
+    S.host_inst_stale = true;
 }
 
 }  // namespace
@@ -374,6 +526,10 @@ int sync_host(Scene& s, bool meshes_only) {
         for (size_t i = 0; i < M.verts.size(); i++) M.verts[i] = mk(buf[i].x, buf[i].y, buf[i].z);
         if (!M.normals.empty()) HIP_OK(hipMemcpy(buf.data(), d->normals + d->nbase[(size_t)m], M.normals.size() * sizeof(float4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < M.normals.size(); i++) M.normals[i] = mk(buf[i].x, buf[i].y, buf[i].z);
+        if (!M.verts2.empty() && M.verts2.size() == M.verts.size() && d->verts2 && s.mesh_blas[(size_t)m] < 0) {   // an async deform's time-1 set
+            HIP_OK(hipMemcpy(buf.data(), d->verts2 + d->vbase[(size_t)m], M.verts2.size() * sizeof(float4), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < M.verts2.size(); i++) M.verts2[i] = mk(buf[i].x, buf[i].y, buf[i].z);
+        }
     }
     s.host_mesh_stale.clear();
     if (s.host_inst_stale && d->refit_ready && d->n_insts == (int)s.instances.size()) {
@@ -397,6 +553,22 @@ int sync_host(Scene& s, bool meshes_only) {
         }
     }
     s.host_inst_stale = false;
+    if (!meshes_only) {   // the BLASes a deform refitted: boxes and triangles (BLAS nodes keep their order on the device)
+        for (int32_t b : s.host_blas_stale) {
+            if ((size_t)b >= d->blas.size() || (size_t)b >= s.blas.size()) continue;
+            const DeviceState::BlasRange& R = d->blas[(size_t)b];
+            Blas& B = s.blas[(size_t)b];
+            std::vector<QNode> DN(R.n_nodes);
+            std::vector<DLeaf> DL(R.n_leaves);
+            if (!DN.empty()) HIP_OK(hipMemcpy(DN.data(), d->nodes + R.node_base, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
+            if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d->leaves + R.leaf_base, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < B.nodes.size() && i < DN.size(); i++) memcpy(B.nodes[i].box, DN[i].box, sizeof B.nodes[i].box);
+            for (size_t i = 0; i < B.leaves.size() && i < DL.size(); i++)
+                for (int k = 0; k < 4; k++)
+                    for (int c = 0; c < 9; c++) B.leaves[i].t[4 * c + k] = DL[i].tri[k][c];
+        }
+        s.host_blas_stale.clear();
+    }
     if (!meshes_only) s.host_bvh_stale = false;
     if (!meshes_only && !s.nodes.empty())
         for (DeviceState* r : s.devs) root_box(s.nodes[0], r->bb_lo, r->bb_hi);
@@ -404,6 +576,64 @@ int sync_host(Scene& s, bool meshes_only) {
     return MRT_OK;
 }
 
+namespace {
+
+// The synchronous entries after their argument checks: mesh `mesh` of `kind` (deform_check;
+// mrt_scene_update_mesh: kDeformWorld) takes verts (verts2: kDeformMotion) and normals.
+int update_sync(Scene& S, int mesh, int kind, const float* verts, const float* verts2, const float* normals, float* refit_ms) {
+    int rc;
+    Mesh& M = S.meshes[(size_t)mesh];
+    const int32_t blas = S.mesh_blas[(size_t)mesh];
+    auto set_host = [&] {
+        refit_set_mesh(M, verts, normals);
+        if (kind == kDeformMotion) deform_set_motion(M, verts2);
+    };
+    const bool on_device = !S.dev_dirty && !S.devs.empty();
+    if (!on_device) {   // built, not uploaded (or a re-upload is due anyway): the same arithmetic on the host
+        if ((rc = sync_host(S))) return rc;
+        set_host();
+        if (kind == kDeformBlas) refit_blas_host(S, blas);   // the BLAS, then the boxes of its instances
+        refit_host(S);
+        return MRT_OK;
+    }
+    if ((rc = sync_host(S, true))) return rc;   // the host mesh is current from here (the hierarchy stays on the device)
+    set_host();
+    const uint32_t nv = (uint32_t)M.verts.size(), nn = normals ? (uint32_t)M.normals.size() : 0u;
+    const uint32_t nv2 = kind == kDeformMotion ? nv : 0u;
+    DeviceState* cur = S.dev ? S.dev : S.devs[0];
+    for (DeviceState* d : S.devs) {
+        HIP_OK(hipSetDevice(d->device));
+        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
+        if ((rc = prepare(S, *d))) return rc;
+        if ((rc = stage_reserve(*d, ((size_t)nv + nn + nv2) * 3))) return rc;
+        if (nv) HIP_OK(hipMemcpy(d->refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (nn) HIP_OK(hipMemcpy(d->refit_stage + (size_t)nv * 3, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (nv2) HIP_OK(hipMemcpy(d->refit_stage + ((size_t)nv + nn) * 3, verts2, (size_t)nv2 * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (!M.tidx.empty() && d->tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
+            std::vector<float4> T(M.tan.size()), B(M.btan.size());
+            for (size_t i = 0; i < T.size(); i++) T[i] = make_float4(M.tan[i].x, M.tan[i].y, M.tan[i].z, 0.f);
+            for (size_t i = 0; i < B.size(); i++) B[i] = make_float4(M.btan[i].x, M.btan[i].y, M.btan[i].z, 0.f);
+            HIP_OK(hipMemcpy(d->tans + d->nbase[(size_t)mesh], T.data(), T.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d->btans + d->nbase[(size_t)mesh], B.data(), B.size() * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
+        if ((rc = enqueue_deform(*d, mesh, kind, blas, d->refit_stage, d->refit_stage + ((size_t)nv + nn) * 3, nv,
+                                 nn ? d->refit_stage + (size_t)nv * 3 : nullptr, nn, (uint32_t)M.nt(), nullptr)))
+            return rc;
+        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
+        HIP_OK(hipEventSynchronize(d->refit_ev1));
+        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
+        QNode root;   // the binning box follows the refitted root
+        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
+        root_box(root, d->bb_lo, d->bb_hi);
+    }
+    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
+    if (kind == kDeformBlas) mark_blas_stale(S, blas);
+    HIP_OK(hipSetDevice(cur->device));
+    return MRT_OK;
+}
+
+}  // namespace
 }  // namespace mrt
 
 using namespace mrt;
@@ -415,45 +645,52 @@ int mrt_scene_update_mesh(mrt_scene* s, int mesh, const float* verts, const floa
     if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
     Scene& S = s->impl;
     if (!verts) { set_error("update_mesh: null vertices"); return MRT_ERR_INVALID; }
-    int rc = refit_check(S, mesh, verts, normals);   // arguments first: no device call before
+    const int rc = refit_check(S, mesh, verts, normals);   // arguments first: no device call before
     if (rc) return rc;
+    return update_sync(S, mesh, kDeformWorld, verts, nullptr, normals, refit_ms);
+}
+
+int mrt_scene_deform_mesh(mrt_scene* s, int mesh, const float* verts, const float* verts2, const float* normals,
+                          float* refit_ms) {
+    if (refit_ms) *refit_ms = 0.f;
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    if (!verts) { set_error("deform_mesh: null vertices"); return MRT_ERR_INVALID; }
+    int kind = kDeformWorld;
+    const int rc = deform_check(S, mesh, verts, verts2, verts2 != nullptr, normals, &kind);   // arguments first
+    if (rc) return rc;
+    return update_sync(S, mesh, kind, verts, verts2, normals, refit_ms);
+}
+
+int mrt_scene_deform_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_verts2, const float* d_normals,
+                                void* stream) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    Scene& S = s->impl;
+    int kind = kDeformWorld;
+    int rc = deform_check(S, mesh, nullptr, nullptr, d_verts2 != nullptr, nullptr, &kind);   // ids and kinds: the arrays are on the device
+    if (rc) return rc;
+    if (kind == kDeformWorld) return mrt_scene_update_mesh_async(s, mesh, d_verts, d_normals, stream);
+    if (!d_verts) { set_error("deform_mesh: null vertices"); return MRT_ERR_INVALID; }
     Mesh& M = S.meshes[(size_t)mesh];
-    const bool on_device = !S.dev_dirty && !S.devs.empty();
-    if (!on_device) {   // built, not uploaded (or a re-upload is due anyway): the same arithmetic on the host
-        if ((rc = sync_host(S))) return rc;
-        refit_set_mesh(M, verts, normals);
-        refit_host(S);
-        return MRT_OK;
+    if (!M.tidx.empty()) {
+        set_error("deform_mesh_async: the mesh has texture coordinates (its tangent frames are recomputed on the host: use mrt_scene_deform_mesh)");
+        return MRT_ERR_INVALID;
     }
-    if ((rc = sync_host(S, true))) return rc;   // the host mesh is current from here (the hierarchy stays on the device)
-    refit_set_mesh(M, verts, normals);
-    const uint32_t nv = (uint32_t)M.verts.size(), nn = normals ? (uint32_t)M.normals.size() : 0u;
-    DeviceState* cur = S.dev ? S.dev : S.devs[0];
-    for (DeviceState* d : S.devs) {
-        HIP_OK(hipSetDevice(d->device));
-        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
-        if ((rc = prepare(S, *d))) return rc;
-        if ((rc = stage_reserve(*d, ((size_t)nv + nn) * 3))) return rc;
-        if (nv) HIP_OK(hipMemcpy(d->refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (nn) HIP_OK(hipMemcpy(d->refit_stage + (size_t)nv * 3, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (!M.tidx.empty() && d->tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
-            std::vector<float4> T(M.tan.size()), B(M.btan.size());
-            for (size_t i = 0; i < T.size(); i++) T[i] = make_float4(M.tan[i].x, M.tan[i].y, M.tan[i].z, 0.f);
-            for (size_t i = 0; i < B.size(); i++) B[i] = make_float4(M.btan[i].x, M.btan[i].y, M.btan[i].z, 0.f);
-            HIP_OK(hipMemcpy(d->tans + d->nbase[(size_t)mesh], T.data(), T.size() * sizeof(float4), hipMemcpyHostToDevice));
-            HIP_OK(hipMemcpy(d->btans + d->nbase[(size_t)mesh], B.data(), B.size() * sizeof(float4), hipMemcpyHostToDevice));
-        }
-        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
-        if ((rc = enqueue(*d, mesh, d->refit_stage, nv, nn ? d->refit_stage + (size_t)nv * 3 : nullptr, nn, nullptr))) return rc;
-        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
-        HIP_OK(hipEventSynchronize(d->refit_ev1));
-        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
-        QNode root;   // the binning box follows the refitted root
-        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
-        root_box(root, d->bb_lo, d->bb_hi);
+    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
+        set_error("deform_mesh_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
+        return MRT_ERR_INVALID;
     }
-    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
-    HIP_OK(hipSetDevice(cur->device));
+    DeviceState& d = *S.dev;
+    HIP_OK(hipSetDevice(d.device));
+    if ((rc = prepare(S, d))) return rc;
+    const int32_t blas = S.mesh_blas[(size_t)mesh];
+    if ((rc = enqueue_deform(d, mesh, kind, blas, d_verts, d_verts2, (uint32_t)M.verts.size(), d_normals,
+                             (uint32_t)M.normals.size(), (uint32_t)M.nt(), (hipStream_t)stream)))
+        return rc;
+    S.host_bvh_stale = true;
+    if (kind == kDeformBlas) mark_blas_stale(S, blas);
+    if (std::find(S.host_mesh_stale.begin(), S.host_mesh_stale.end(), mesh) == S.host_mesh_stale.end())
+        S.host_mesh_stale.push_back(mesh);
     return MRT_OK;
 }
 
@@ -489,7 +726,9 @@ int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n, cons
     Scene& S = s->impl;
     if (!m16s) { set_error("update_instances: null matrices"); return MRT_ERR_INVALID; }
     std::vector<Instance> NI;   // arguments first: no device call and no change before
-    int rc = instances_check(S, ids, 0, n, m16s, &NI);
+    int rc;
+    if (!S.host_blas_stale.empty() && (rc = sync_host(S))) return rc;   // the boxes come from the BLAS roots: a device deform is ahead
+    rc = instances_check(S, ids, 0, n, m16s, &NI);
     if (rc) return rc;
     if (n == 0) return MRT_OK;
     auto apply = [&] {

@@ -121,7 +121,12 @@ struct Scene {
     bool host_bvh_stale = false;
     std::vector<int32_t> host_mesh_stale;
     bool host_inst_stale = false;
-    bool host_stale() const { return host_bvh_stale || !host_mesh_stale.empty() || host_inst_stale; }
+    // After mrt_scene_deform_mesh on an uploaded scene the nodes and leaves of these BLASes
+    // are behind the replica's (and with them the boxes of their instances: host_inst_stale).
+    std::vector<int32_t> host_blas_stale;
+    bool host_stale() const {
+        return host_bvh_stale || !host_mesh_stale.empty() || host_inst_stale || !host_blas_stale.empty();
+    }
 
     // device replicas (one per HIP device used, mrt_render_opts.devices); `dev` is
     // the one the last call used.  dev_dirty: the host scene changed, every
@@ -144,9 +149,14 @@ int add_instance(Scene& s, int32_t blas, const float* m16, std::string& err);
 // m, inv, inv_t and box of I from the row-major 4x4 m16 and the root of BLAS I.blas
 // (add_instance's arithmetic; mrt_scene_update_instances uses it for a built scene)
 void instance_set_matrix(const Scene& s, Instance& I, const float* m16);
+// Its box half: ProxyObject::getAABB of BLAS root r under the row-major 4x4 m16 (min xyz, max xyz)
+void instance_box(const QNode& r, const float* m16, float box[6]);
 // The refit on the host: the world leaf triangles from the meshes' vertices (make_leaf),
 // then every box bottom-up, topology kept (the arithmetic of mrt_refit.hip's kernels).
 void refit_host(Scene& s);
+// The same for BLAS b from its meshes' vertices, then Instance::box of every instance of b
+// from the refitted root and the instance's m_transform (mrt_scene_deform_mesh).
+void refit_blas_host(Scene& s, int32_t b);
 // The box the build gave world object o when it is a ProxyObject or an MBObject lane
 // (Builder::tri_aabb): min xyz, max xyz.  False for a plain triangle.
 bool fixed_lane_box(const Scene& s, int32_t o, float box[6]);
@@ -164,6 +174,12 @@ int instances_check(const Scene& s, const int32_t* ids, int32_t first, int32_t n
 // form, whose arrays are on the device), and the new arrays into the host mesh
 int refit_check(const Scene& s, int mesh, const float* verts, const float* normals);
 void refit_set_mesh(Mesh& m, const float* verts, const float* normals);
+// host_api.cpp: the argument checks of mrt_scene_deform_mesh (verts == nullptr: the async form,
+// which passes has_verts2 for its device pointer).  kind: kDeformWorld, kDeformBlas or kDeformMotion.
+enum { kDeformWorld = 0, kDeformBlas = 1, kDeformMotion = 2 };
+int deform_check(const Scene& s, int mesh, const float* verts, const float* verts2, bool has_verts2,
+                 const float* normals, int* kind);
+void deform_set_motion(Mesh& m, const float* verts2);
 // host_texture.cpp
 int load_hdr(const char* path, int& W, int& H, std::vector<float>* rgb, std::string& err);
 int build_dome(const Texture& t, DomeTables& d, std::string& err);

@@ -277,7 +277,15 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
     };
     append(s.nodes, s.leaves, &s.obj_inst, nullptr);
     std::vector<int32_t> blas_root(s.blas.size());
-    for (size_t b = 0; b < s.blas.size(); b++) blas_root[b] = append(s.blas[b].nodes, s.blas[b].leaves, nullptr, &s.blas[b]);
+    d.blas.assign(s.blas.size(), DeviceState::BlasRange());
+    for (size_t b = 0; b < s.blas.size(); b++) {
+        d.blas[b].leaf_base = (uint32_t)DL.size();
+        blas_root[b] = append(s.blas[b].nodes, s.blas[b].leaves, nullptr, &s.blas[b]);
+        d.blas[b].n_nodes = (uint32_t)s.blas[b].nodes.size();
+        d.blas[b].n_leaves = (uint32_t)s.blas[b].leaves.size();
+        d.blas[b].shade_base = shade_base[b];
+    }
+    d.n_leaves_all = (uint32_t)DL.size();
     // The world hierarchy's first kLdsNodes nodes in breadth-first order get device
     // numbers 0 .. kLdsNodes - 1 (frame1_kernel<LN> stages them in LDS).  Device node
     // numbers are internal: the visit order follows the child slots, not the numbers.
@@ -312,6 +320,7 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
         for (int32_t& br : blas_root) br = perm[(size_t)br];
         d.node_perm.assign(perm.begin(), perm.begin() + (ptrdiff_t)nw);
     }
+    for (size_t b = 0; b < s.blas.size(); b++) d.blas[b].node_base = (uint32_t)blas_root[b];   // BLAS nodes keep their numbers
     d.n_world_nodes = (uint32_t)nw;
     d.n_world_leaves = (uint32_t)s.leaves.size();
     d.vbase = vbase;

@@ -742,6 +742,44 @@ class Scene:
                                       C.byref(ms)), "updateMesh")
         return float(ms.value)
 
+    def deformMesh(self, mesh_id: int, verts, normals=None, verts2=None, stream=None):
+        """New vertices (and normals) for any mesh `mesh_id`, same counts and topology
+        (mrt_scene_deform_mesh).  A plain world mesh: what updateMesh does.  A mesh of a BLAS
+        (setupProxy / setupMultiProxy): that BLAS refitted in place, the box of each of its
+        instances recomputed from the new root, the world hierarchy refitted.  A motion-blurred
+        world mesh (makeMBMeshObjs): `verts` at time 0 and `verts2` at time 1, both required; its
+        MBObject boxes are recomputed, the world hierarchy refitted.  verts2 is refused elsewhere.
+        numpy arrays go through the synchronous entry, which returns the device time of the
+        kernels in ms (0.0 for a scene not yet uploaded: the host refits).  torch device tensors
+        (contiguous float32 on the scene's device) go through mrt_scene_deform_mesh_async on
+        `stream` (a torch stream; default: the current one) without a host copy or a
+        synchronisation, and return None; the mesh must have no texture coordinates."""
+        L = lib()
+        nv, nn, nt = C.c_int32(), C.c_int32(), C.c_int32()
+        check(L.mrt_scene_mesh_info(self.handle, int(mesh_id), C.byref(nv), C.byref(nn), C.byref(nt)), "deformMesh")
+        for x, n, what in ((verts, nv.value, "verts"), (verts2, nv.value, "verts2"), (normals, nn.value, "normals")):
+            if x is not None and int(np.prod(tuple(x.shape))) != 3 * n:
+                raise MRTError(f"deformMesh: {what} must hold {n} x 3 floats (the mesh's own count)")
+        if hasattr(verts, "data_ptr"):
+            import torch
+            for x in (verts, verts2, normals):
+                if x is not None and not (hasattr(x, "data_ptr") and x.is_cuda and x.dtype == torch.float32
+                                          and x.is_contiguous() and x.device.index == self.device):
+                    raise MRTError("deformMesh: tensors must be contiguous float32 on the scene's device")
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            st = (stream if stream is not None else torch.cuda.current_stream(verts.device)).cuda_stream
+            check(L.mrt_scene_deform_mesh_async(self.handle, int(mesh_id), verts.data_ptr(),
+                                                verts2.data_ptr() if verts2 is not None else None,
+                                                normals.data_ptr() if normals is not None else None, st), "deformMesh")
+            return None
+        v = np.ascontiguousarray(verts, np.float32)
+        v2 = np.ascontiguousarray(verts2, np.float32) if verts2 is not None else None
+        n = np.ascontiguousarray(normals, np.float32) if normals is not None else None
+        ms = C.c_float(0.0)
+        check(L.mrt_scene_deform_mesh(self.handle, int(mesh_id), v.ctypes.data, v2.ctypes.data if v2 is not None else None,
+                                      n.ctypes.data if n is not None else None, C.byref(ms)), "deformMesh")
+        return float(ms.value)
+
     def updateInstances(self, matrices, ids=None, first=0, stream=None):
         """New m_transform matrices for ProxyObject instances of the built scene
         (ProxyMatrix::set, then a refit where the reference rebuilds; mrt_scene_update_instances):

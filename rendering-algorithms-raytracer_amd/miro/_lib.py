@@ -33,7 +33,7 @@ EXPORTS = [
     "mrt_trace_rays", "mrt_trace_rays_async", "mrt_shade_hits", "mrt_shade_hits_async", "mrt_hit_surfaces",
     "mrt_hit_surfaces_async", "mrt_scene_update_mesh", "mrt_scene_update_mesh_async",
     "mrt_scene_update_instances", "mrt_scene_update_instances_async", "mrt_scene_instance_count",
-    "mrt_scene_instance_info",
+    "mrt_scene_instance_info", "mrt_scene_deform_mesh", "mrt_scene_deform_mesh_async",
 ]
 
 
@@ -221,6 +221,9 @@ def load():
         L.mrt_scene_update_instances_async.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.mrt_scene_instance_count.argtypes = [C.c_void_p]
         L.mrt_scene_instance_info.argtypes = [C.c_void_p, C.c_int32, _ip, _fp, _fp, _fp, _fp]
+    if hasattr(L, "mrt_scene_deform_mesh"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_scene_deform_mesh.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.mrt_scene_deform_mesh_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
