@@ -1396,6 +1396,12 @@ typedef struct {
     uint32_t shadow_mask;
     float time;                     /* the camera ray's time (getTimeSample), inherited by every ray of it */
     float shadow_time;              /* the time sampleLight's shadow rays get: time, or .001 for translucency */
+    /* the draw log (oro_render_logged; off when log_on == 0): this pixel's own storage, so
+     * pixels rendered on different threads never share any */
+    int log_on;
+    uint32_t* log;                  /* (skey, dim) of every next_rand call, in call order */
+    uint32_t log_n, log_cap;        /* draws logged / allocated */
+    uint32_t max_ior;               /* debug counter: the deepest IOR-history index a shade() call saw */
 } shade_ctx;
 
 /* Counter RNG keys: every shade() call (one chain level of one path) draws from
@@ -1403,7 +1409,19 @@ typedef struct {
  * counts -- the order-free form the device's wavefront passes need.  The
  * reference draws one global sequence (src/Scene.cpp:39-47); both are
  * independent uniforms per draw. */
-static float next_rand(shade_ctx* c) { return oro_rand(c->pixel, c->skey, c->dim++, 0x5EEDu); }
+static void log_draw(shade_ctx* c) {
+    if (c->log_n == c->log_cap) {
+        uint32_t cap = c->log_cap ? c->log_cap * 2 : 64;
+        uint32_t* p = (uint32_t*)realloc(c->log, (size_t)cap * 2 * sizeof(uint32_t));
+        if (!p) { c->log_on = -1; return; }     /* out of memory: oro_render_logged reports it */
+        c->log = p; c->log_cap = cap;
+    }
+    c->log[2 * c->log_n] = c->skey; c->log[2 * c->log_n + 1] = c->dim; c->log_n++;
+}
+static float next_rand(shade_ctx* c) {
+    if (c->log_on > 0) log_draw(c);
+    return oro_rand(c->pixel, c->skey, c->dim++, 0x5EEDu);
+}
 /* branch: the dispersion branch code of the shade() call (0 outside dispersive
  * splits; each split appends its child index + 1 in two bits), so sibling rays
  * at one level draw from their own keys */
@@ -1785,6 +1803,7 @@ static v3 path_trace(shade_ctx* c, const oro_material* mat, v3 P, v3 theNormal, 
 static v3 shade_blinn(shade_ctx* c, const oro_material* mat, const ray_t* r, const hit_t* h, ior_list* ior,
                       chain_t ch) {
     begin_level(c, ch.level, ch.branch);
+    if (ior->idx > c->max_ior) c->max_ior = ior->idx;
     v3 Ld = V(0, 0, 0), Ls = V(0, 0, 0), Lr = V(0, 0, 0), Lt = V(0, 0, 0), translucency = V(0, 0, 0);
     v3 rayD = V(r->d[0], r->d[1], r->d[2]);
     v3 viewDir = vneg(rayD);
@@ -2099,8 +2118,12 @@ static v3 adaptive_levels(shade_ctx* c, const cam_basis* b, int x, int y, v3 sha
     return shadeResult;
 }
 
-int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, int y0, int x1, int y1,
-               float* rgb, uint8_t* rgb8, oro_hit* hitout, uint32_t* shadow, uint64_t* counters, int n_threads) {
+/* oro_render and oro_render_logged.  logs (nullable): W*H slots; each rendered pixel leaves its own
+ * malloc'd key array, its draw count and its deepest IOR-history index there. */
+typedef struct { uint32_t* keys; uint32_t n, max_ior; } pixel_log;
+static int render_impl(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, int y0, int x1, int y1,
+               float* rgb, uint8_t* rgb8, oro_hit* hitout, uint32_t* shadow, uint64_t* counters, int n_threads,
+               pixel_log* logs) {
     if (!s->built || W <= 0 || H <= 0) return -1;
     if (x0 < 0) x0 = 0;
     if (y0 < 0) y0 = 0;
@@ -2118,6 +2141,7 @@ int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, 
         for (int x = x0; x < x1; x++) {
             shade_ctx c; memset(&c, 0, sizeof c);
             c.s = s; c.pixel = (uint32_t)(y * W + x);
+            c.log_on = logs != NULL;
             begin_camera(&c);
             ray_t r = eye_ray(&c, &b, x, y, 0.5f, 0.5f, 0.5f, 0.5f);
             hit_t h;
@@ -2130,6 +2154,15 @@ int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, 
             if (rgb8) { rgb8[3 * p] = map_channel(col.x); rgb8[3 * p + 1] = map_channel(col.y); rgb8[3 * p + 2] = map_channel(col.z); }
             if (hitout) { hitout[p].t = h.t; hitout[p].a = h.a; hitout[p].b = h.b; hitout[p].prim = h.prim >= 0 ? hit_id(s, &h) : -1; }
             if (shadow) shadow[p] = c.shadow_mask;
+            if (logs) {
+                logs[p].keys = c.log; logs[p].n = c.log_n; logs[p].max_ior = c.max_ior;
+                if (c.log_on < 0) {
+#ifdef _OPENMP
+#pragma omp atomic write
+#endif
+                    err = -2;
+                }
+            }
             prim += eye; shadowr += c.shadow_rays; second += c.secondary_rays; nodes += nv + c.nodes; leaves += lv + c.leaves;
             pnodes += nv; pleaves += lv;
         }
@@ -2139,4 +2172,50 @@ int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, 
         counters[4] += pnodes; counters[5] += pleaves; counters[6] += second;
     }
     return err;
+}
+
+int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H, int x0, int y0, int x1, int y1,
+               float* rgb, uint8_t* rgb8, oro_hit* hitout, uint32_t* shadow, uint64_t* counters, int n_threads) {
+    return render_impl(s, cam, W, H, x0, y0, x1, y1, rgb, rgb8, hitout, shadow, counters, n_threads, NULL);
+}
+
+/* The whole frame with the draw log on.  Safe with n_threads > 1: every pixel logs into storage of
+ * its own, gathered here in pixel order once all are done. */
+int oro_render_logged(const oro_scene* s, const oro_camera* cam, int W, int H, float* rgb, uint8_t* rgb8,
+                      int n_threads, uint32_t* counts, uint32_t* max_ior, uint32_t** keys, uint64_t* n_keys) {
+    if (W <= 0 || H <= 0 || !counts || !keys || !n_keys) return -1;
+    const size_t np = (size_t)W * H;
+    pixel_log* logs = (pixel_log*)calloc(np, sizeof(pixel_log));
+    if (!logs) return -2;
+    int rc = render_impl(s, cam, W, H, 0, 0, W, H, rgb, rgb8, NULL, NULL, NULL, n_threads, logs);
+    uint64_t total = 0;
+    for (size_t p = 0; p < np; p++) total += logs[p].n;
+    uint32_t* all = rc == 0 ? (uint32_t*)malloc((size_t)(total ? total : 1) * 2 * sizeof(uint32_t)) : NULL;
+    if (rc == 0 && !all) rc = -2;
+    uint64_t at = 0;
+    for (size_t p = 0; p < np; p++) {
+        if (rc == 0) {
+            if (logs[p].n) memcpy(all + 2 * at, logs[p].keys, (size_t)logs[p].n * 2 * sizeof(uint32_t));
+            counts[p] = logs[p].n;
+            if (max_ior) max_ior[p] = logs[p].max_ior;
+            at += logs[p].n;
+        }
+        free(logs[p].keys);
+    }
+    free(logs);
+    if (rc != 0) return rc;
+    *keys = all; *n_keys = total;
+    return 0;
+}
+void oro_log_free(uint32_t* keys) { free(keys); }
+
+/* Image::linear_to_gammaF, the float twin of oro_gamma_table */
+void oro_gamma_table_f(float* out) {
+    oro_gamma_table(NULL);
+    memcpy(out, g_lutF, sizeof g_lutF);
+}
+/* Map() (src/Image.cpp:71-76) of n floats, as rgb8 is written */
+void oro_map_channel(size_t n, const float* in, uint8_t* out) {
+    oro_gamma_table(NULL);
+    for (size_t i = 0; i < n; i++) out[i] = map_channel(in[i]);
 }

@@ -144,6 +144,19 @@ int oro_render(const oro_scene* s, const oro_camera* cam, int W, int H,
                float* rgb, uint8_t* rgb8, oro_hit* hit, uint32_t* shadow,
                uint64_t* counters, int n_threads);
 
+/* The whole frame with the draw log on: the arithmetic of oro_render (same bits), and for every
+ * pixel the (skey, dim) of each oro_rand draw it took, two uint32 per draw, in call order, the
+ * camera's draws and every eye ray of the adaptive levels included.  In call order these are the
+ * values the reference reads from Scene::rands[] for that pixel.
+ * counts[W*H]: draws per pixel; max_ior[W*H] (nullable): the deepest IOR-history index
+ * (Ray::IORList) a Blinn::shade call of the pixel saw, a debug counter; *keys: malloc'd,
+ * 2 * *n_keys uint32, pixels in row-major order (pixel p's draws start at the sum of the counts
+ * before it), to be released with oro_log_free.
+ * Safe with n_threads > 1: each pixel logs into its own storage. */
+int oro_render_logged(const oro_scene* s, const oro_camera* cam, int W, int H, float* rgb, uint8_t* rgb8,
+                      int n_threads, uint32_t* counts, uint32_t* max_ior, uint32_t** keys, uint64_t* n_keys);
+void oro_log_free(uint32_t* keys);
+
 /* image-based lighting (src/hdrloader.cpp, src/Texture.cpp, src/DomeLight.*) -- */
 /* HDRLoader::load: header only (sizes), then W*H*3 floats, row 0 = top.
  * 0 on success, negative on error (oro_ibl.c lists the rejected inputs). */
@@ -191,6 +204,8 @@ float oro_x86_rsqrt(float x);
 float oro_rcp_nr(float x);
 float oro_rsqrt_nr(float x);
 void oro_gamma_table(uint8_t* lut32769);
+void oro_gamma_table_f(float* lutF32769);                          /* Image::linear_to_gammaF */
+void oro_map_channel(size_t n, const float* in, uint8_t* out);     /* Map(), src/Image.cpp:71-76 */
 /* counter-based RNG used in place of the reference's global MT pool.  Keys:
  * skey = eye-ray sample * 1024 + path, dim = (chain level + 1) << 24 | k for the
  * k-th draw of one shade() call (the camera ray's draws are dims 0-2). */

@@ -115,6 +115,12 @@ def _declare(L):
     L.oro_trace.argtypes = [C.c_void_p, C.c_size_t, _fp, _fp, _fp, _fp, C.c_void_p, _u32p, _u32p]
     L.oro_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              _fp, _u8p, C.c_void_p, _u32p, _u64p, C.c_int]
+    L.oro_render_logged.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_int, _fp, _u8p, C.c_int, _u32p, _u32p,
+                                    C.POINTER(_u32p), _u64p]
+    L.oro_log_free.argtypes = [_u32p]
+    L.oro_log_free.restype = None
+    L.oro_gamma_table_f.argtypes = [_fp]
+    L.oro_map_channel.argtypes = [C.c_size_t, _fp, _u8p]
     for n in ("oro_x86_rcp", "oro_x86_rsqrt", "oro_rcp_nr", "oro_rsqrt_nr"):
         getattr(L, n).argtypes = [C.c_float]
         getattr(L, n).restype = C.c_float
@@ -450,16 +456,38 @@ class OracleScene:
             raise RuntimeError(f"oracle trace failed ({r})")
         return out, nv, lv
 
-    def render(self, cam, W, H, rect=None, threads=1, want_hits=True, libm=None):
+    def render(self, cam, W, H, rect=None, threads=1, want_hits=True, libm=None, draw_log=False):
         """cam: dict(eye, lookAt, up, fov[, aperture, focusPlane, shutterSpeed]).  Returns dict of numpy arrays.
-        libm: LIBM_FLOAT / LIBM_DOUBLE (None: the module default, set_default_libm)."""
+        libm: LIBM_FLOAT / LIBM_DOUBLE (None: the module default, set_default_libm).
+        draw_log: the whole frame with the draw log on (oro_render_logged; any thread count, each
+        pixel logs into its own storage): dict of rgb, rgb8, draw_keys (n, 2) uint32 (skey, dim) of
+        every draw in call order, pixels row-major, draw_offsets (W * H + 1,) int64 (pixel p's draws
+        are draw_keys[draw_offsets[p]:draw_offsets[p + 1]]) and max_ior (H, W), the deepest
+        IOR-history index a Blinn shade() call of the pixel saw."""
         _apply_libm(libm)
         c = Camera(_v3(cam["eye"]), _v3(cam.get("up", (0, 1, 0))), _v3(cam["lookAt"]), float(cam["fov"]),
                    float(cam.get("aperture", 0.0)), float(cam.get("focusPlane", 1.0)),
                    float(cam.get("shutterSpeed", 0.001)))
-        x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         rgb = np.zeros((H, W, 3), np.float32)
         rgb8 = np.zeros((H, W, 3), np.uint8)
+        if draw_log:
+            if rect is not None:
+                raise ValueError("the draw log covers whole frames")
+            counts = np.zeros(W * H, np.uint32)
+            max_ior = np.zeros((H, W), np.uint32)
+            keys, n = _u32p(), C.c_uint64()
+            r = self.L.oro_render_logged(self.h, C.byref(c), W, H, _p(rgb, _fp), _p(rgb8, _u8p), int(threads),
+                                         _p(counts, _u32p), _p(max_ior, _u32p), C.byref(keys), C.byref(n))
+            if r != 0:
+                raise RuntimeError(f"oracle render failed ({r})")
+            try:
+                k = np.ctypeslib.as_array(keys, shape=(max(int(n.value), 1), 2))[:int(n.value)].copy()
+            finally:
+                self.L.oro_log_free(keys)
+            off = np.zeros(W * H + 1, np.int64)
+            np.cumsum(counts, out=off[1:])
+            return {"rgb": rgb, "rgb8": rgb8, "draw_keys": k, "draw_offsets": off, "max_ior": max_ior}
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, W, H)
         hits = np.zeros((H, W), HIT_DTYPE) if want_hits else None
         shadow = np.zeros((H, W), np.uint32)
         counters = np.zeros(7, np.uint64)
@@ -508,3 +536,18 @@ def gamma_table():
     t = np.zeros(32769, np.uint8)
     lib().oro_gamma_table(_p(t, _u8p))
     return t
+
+
+def gamma_table_f():
+    """Image::linear_to_gammaF as the oracle holds it: 32769 floats."""
+    t = np.zeros(32769, np.float32)
+    lib().oro_gamma_table_f(_p(t, _fp))
+    return t
+
+
+def map_channel(x):
+    """Map() (src/Image.cpp:71-76) of each float: the byte rgb8 gets."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.zeros(len(x), np.uint8)
+    lib().oro_map_channel(len(x), _p(x, _fp), _p(out, _u8p))
+    return out

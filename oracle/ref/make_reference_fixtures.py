@@ -79,6 +79,28 @@ def main():
             "held_out_bias": round(held["bias"], 6), "held_out_max_z": round(held["max_z"], 6),
             "z_bound": round(held["bound"], 6), "values_with_s_gt_0": held["n"]}
     RC.save_npz(os.path.join(RC.REF_DIR, "statistical.npz"), stat)
+    # every chain level: adaptiveSampleScene on the oracle's logged draws (ref_driver replaylog), the
+    # gamma tables, Map() and the image decoders
+    deep = {}
+    meta["deep"] = {"frames": {}, "decode": {}}
+    for name, case in RC.deep_cases().items():
+        Os, Rs = RC.build_scenes(case, True)
+        w, h = RC.case_size(case)
+        log = Os.render(RC.case_camera(case), w, h, draw_log=True)
+        ref = Rs.replay_log(RC.case_camera(case), w, h, log)
+        Rs.close()
+        assert ref["consumed"].max() < 65536
+        deep[name + ".rgb"], deep[name + ".rgb8"] = ref["rgb"], ref["rgb8"]
+        deep[name + ".draws"] = ref["consumed"].astype(np.uint16)
+        meta["deep"]["frames"][name] = {"size": [w, h], "driver": "replaylog", "sha256": RC.sha(ref["rgb"]),
+                                        "max_draws": int(ref["consumed"].max())}
+    deep["gamma.u8"], deep["gamma.f32"] = refdriver.gamma_tables()
+    deep["map.in"] = RC.map_inputs()
+    deep["map.out"] = refdriver.map_values(deep["map.in"])
+    RC.save_npz(os.path.join(RC.REF_DIR, "deep.npz"), deep)
+    for name, path in sorted(RC.decode_images().items()):
+        a = refdriver.decode(path)
+        meta["deep"]["decode"][name] = {"shape": list(a.shape), "sha256": RC.sha(a)}
     with open(os.path.join(RC.REF_DIR, "reference.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
         f.write("\n")

@@ -11,12 +11,18 @@
 //   ref_driver render SCENE OUT                   adaptiveSampleScene per pixel, free-running RNG
 //   ref_driver replay SCENE OUT                   one sample per pixel on the oracle's draws
 //   ref_driver repeat SCENE K OUT                 K free-running renders, one RNG stream running on
+//   ref_driver replaylog SCENE LOG OUT            adaptiveSampleScene per pixel on the oracle's logged draws
+//   ref_driver gamma  OUT                         Image::linear_to_gamma (32769 bytes), linear_to_gammaF (32769 floats)
+//   ref_driver map    IN N OUT                    Map() of N floats: a 1-row image, setPixel, getCharPixels
+//   ref_driver version                           the digest of the sources this driver was built from
+//   ref_driver decode FILE OUT                    RawImage::loadImage: width, height, channels (int32), the floats
 //
 // SCENE is the text format oracle/refdriver.py writes: one command per line, integers in
 // decimal, floats as the 8 hex digits of their bits, arrays in raw little-endian side files.
 // Single-threaded by construction: every call passes thread 0 (run with OMP_NUM_THREADS=1).
 #include <stdint.h>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <new>
 #include <sstream>
@@ -39,6 +45,10 @@
 #include "RawImage.h"
 #include "Texture.h"
 #include "BVH.h"
+
+#ifndef DRIVER_SUM
+#define DRIVER_SUM "unknown"
+#endif
 
 extern "C" float oro_rand(uint32_t pixel, uint32_t sample, uint32_t dim, uint32_t seed);
 
@@ -349,6 +359,83 @@ void replay_frame(Loaded& S, float* rgb) {
     });
 }
 
+// Every chain level on the oracle's draws.  LOG: W*H uint32 draw counts (pixels row-major), then
+// (skey, dim) uint32 pairs of every draw in the oracle's call order.  The oracle's next_rand sites
+// are in the order of the reference's getRand sites, so pixel p's k-th logged key is the k-th value
+// the reference reads from the pool: the pool gets oro_rand of those keys, NaN after them (a draw
+// too many shows in the colour), and the whole of adaptiveSampleScene runs from read position 0.
+// OUT: W*H*3 floats, the W*H*3 bytes Image::setPixel stored, W*H uint32 draws consumed.
+void replay_log_frame(Loaded& S, const char* log_path, const char* out_path) {
+    const uint32_t seed = 0x5EEDu;
+    const int POOL = 65536;                        // thread 0's pool; getRand regenerates it at this read position
+    const size_t np = (size_t)S.W * S.H;
+    std::vector<char> head = slurp(log_path, np * 4);
+    const uint32_t* counts = (const uint32_t*)head.data();
+    std::vector<uint64_t> first(np + 1, 0);
+    for (size_t p = 0; p < np; p++) {
+        if (counts[p] >= (uint32_t)POOL) Tok::die("a pixel logs 65536 draws or more: the pool wraps there");
+        first[p + 1] = first[p] + counts[p];
+    }
+    std::vector<char> raw = slurp(log_path, np * 4 + first[np] * 8);
+    const uint32_t* keys = (const uint32_t*)(raw.data() + np * 4);
+    std::vector<float> rgb(np * 3);
+    std::vector<uint32_t> consumed(np);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    Ray ray(0);
+    HitInfo hit;
+    for_each_pixel(S.W, S.H, [&](int i, int j) {
+        const size_t p = (size_t)j * S.W + i;
+        const uint32_t* k = keys + 2 * first[p];
+        const int n = (int)counts[p];
+        for (int d = 0; d < n; d++) Scene::rands[d] = oro_rand((uint32_t)p, k[2 * d], k[2 * d + 1], seed);
+        for (int d = n; d < POOL; d++) Scene::rands[d] = nan;
+        Scene::randsIdx[0] = 0;
+        Vector3 c = g_scene->adaptiveSampleScene(0, S.cam, S.img, ray, hit, i, j);
+        consumed[p] = (uint32_t)Scene::randsIdx[0];
+        S.img->setPixel(i, j, c);
+        rgb[3 * p] = c.x; rgb[3 * p + 1] = c.y; rgb[3 * p + 2] = c.z;
+    });
+    std::vector<char> out((const char*)rgb.data(), (const char*)(rgb.data() + rgb.size()));
+    const char* px = (const char*)S.img->getCharPixels();
+    out.insert(out.end(), px, px + np * 3);
+    out.insert(out.end(), (const char*)consumed.data(), (const char*)(consumed.data() + np));
+    spill(out_path, out.data(), out.size());
+}
+
+int cmd_gamma(const char* out_path) {
+    Image img;                                     // its constructor runs generateGammaTables
+    std::vector<char> out((const char*)Image::linear_to_gamma, (const char*)Image::linear_to_gamma + 32769);
+    out.insert(out.end(), (const char*)Image::linear_to_gammaF, (const char*)(Image::linear_to_gammaF + 32769));
+    spill(out_path, out.data(), out.size());
+    return 0;
+}
+
+int cmd_map(const char* in_path, int n, const char* out_path) {
+    std::vector<char> raw = slurp(in_path, (size_t)n * 4);
+    const float* x = (const float*)raw.data();
+    Image img;
+    img.resize(n, 1);
+    for (int i = 0; i < n; i++) img.setPixel(i, 0, Vector3(x[i], x[i], x[i]));
+    spill(out_path, img.getCharPixels(), (size_t)n * 3);
+    return 0;
+}
+
+// RawImage::loadImage, the loader behind every Texture of the reference's scene scripts (material
+// maps and Scene::setEnvMap alike); TGA decoding reads Image::gamma_to_linear, so an Image first.
+int cmd_decode(char* file, const char* out_path) {
+    Image img;
+    RawImage r;
+    r.m_rawData = 0; r.m_width = r.m_height = 0;
+    r.loadImage(file);
+    if (!r.m_rawData || r.m_width <= 0 || r.m_height <= 0) return 3;
+    const int32_t ch = r.m_imageType == GRAYSCALE ? 1 : r.m_imageType == RGBA ? 4 : 3;
+    const int32_t head[3] = {r.m_width, r.m_height, ch};
+    std::vector<char> out((const char*)head, (const char*)(head + 3));
+    out.insert(out.end(), (const char*)r.m_rawData, (const char*)(r.m_rawData + (size_t)r.m_width * r.m_height * ch));
+    spill(out_path, out.data(), out.size());
+    return 0;
+}
+
 // TriangleMesh::load and TriangleMesh::preCalc of one OBJ.  The mesh keeps no array lengths, so
 // they are recounted here from the file the way the loader sizes its arrays (lines that begin
 // "v", "vn", "vt"); a file without normals gets the loader's own, counted by the indices.
@@ -391,9 +478,13 @@ int cmd_load(char** a) {
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 2 && std::string(argv[1]) == "version") { puts(DRIVER_SUM); return 0; }
     if (argc < 3) Tok::die("usage: ref_driver COMMAND ...");
     const std::string cmd = argv[1];
     if (cmd == "load" && argc == 4) return cmd_load(argv + 2);
+    if (cmd == "gamma" && argc == 3) return cmd_gamma(argv[2]);
+    if (cmd == "map" && argc == 5) return cmd_map(argv[2], atoi(argv[3]), argv[4]);
+    if (cmd == "decode" && argc == 4) return cmd_decode(argv[2], argv[3]);
     Loaded S;
     load_scene(argv[2], S);
     if (cmd == "bvh" && argc == 4) {
@@ -410,6 +501,8 @@ int main(int argc, char** argv) {
         std::vector<float> rgb((size_t)S.W * S.H * 3);
         if (cmd == "render") render_frame(S, rgb.data()); else replay_frame(S, rgb.data());
         spill(argv[3], rgb.data(), rgb.size() * 4);
+    } else if (cmd == "replaylog" && argc == 5) {
+        replay_log_frame(S, argv[3], argv[4]);
     } else if (cmd == "repeat" && argc == 5) {
         const int K = atoi(argv[3]);
         std::vector<float> rgb((size_t)K * S.W * S.H * 3);

@@ -50,7 +50,38 @@ def toolchain():
     return {"compiler": cxx, "flags": flags, "libc": " ".join(platform.libc_ver()), "host_cpu_fma": fma}
 
 
+_current = None
+
+
+def _ensure_current():
+    """The driver must be the one oracle/ref's sources build: it prints the digest it was built
+    from (ref_driver version), the Makefile prints the sources' (make sum).  A driver left over
+    from other sources is rebuilt where the reference is at hand; one that still differs is an
+    error, never a driver to take answers from."""
+    global _current
+    if _current:
+        return
+
+    def digests():
+        want = subprocess.run(["make", "-s", "-C", MAKE_DIR, "sum"], stdout=subprocess.PIPE, text=True).stdout.strip()
+        r = subprocess.run([DRIVER, "version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        return want, (r.stdout.strip() if r.returncode == 0 else "none (%s)" % r.stdout.strip()[-200:])
+    want, have = digests()
+    if want != have and reference_present():
+        r = subprocess.run(["make", "-s", "-C", MAKE_DIR, "MRT_REFERENCE=" + reference_root()], stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True)
+        built = r.stdout[-2000:]
+        want, have = digests()
+    else:
+        built = ""
+    if want != have:
+        raise RuntimeError("oracle/_ref/ref_driver was built from other sources (digest %s, oracle/ref has %s) and "
+                           "make -C oracle/ref did not replace it: %s" % (have, want, built))
+    _current = want
+
+
 def _run(args):
+    _ensure_current()
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run([DRIVER] + [str(a) for a in args], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if r.returncode != 0:
@@ -98,6 +129,44 @@ def load_obj(path):
         m["bitangents"] = take(nn, "<f4", 3)
     assert off == len(raw)
     return m
+
+
+def _one_shot(args_of):
+    d = tempfile.mkdtemp(prefix="refdrv_")
+    try:
+        out = os.path.join(d, "out.bin")
+        _run(args_of(d, out))
+        return open(out, "rb").read()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def gamma_tables():
+    """(Image::linear_to_gamma (32769,) uint8, Image::linear_to_gammaF (32769,) float32)."""
+    raw = _one_shot(lambda d, out: ["gamma", out])
+    assert len(raw) == 32769 * 5
+    return np.frombuffer(raw, np.uint8, 32769).copy(), np.frombuffer(raw[32769:], "<f4").copy()
+
+
+def map_values(x):
+    """Map() of each float (src/Image.cpp:71-76), through Image::setPixel on a 1-row image: uint8."""
+    x = np.ascontiguousarray(x, "<f4").reshape(-1)
+
+    def args(d, out):
+        x.tofile(os.path.join(d, "in.bin"))
+        return ["map", os.path.join(d, "in.bin"), len(x), out]
+    raw = _one_shot(args)
+    px = np.frombuffer(raw, np.uint8).reshape(len(x), 3)
+    assert (px[:, 0] == px[:, 1]).all() and (px[:, 0] == px[:, 2]).all()
+    return px[:, 0].copy()
+
+
+def decode(path):
+    """RawImage::loadImage(path): (H, W, channels) float32."""
+    assert " " not in path
+    raw = _one_shot(lambda d, out: ["decode", path, out])
+    w, h, ch = struct.unpack_from("<3i", raw, 0)
+    return np.frombuffer(raw, "<f4", w * h * ch, 12).reshape(h, w, ch).copy()
 
 
 class RefScene:
@@ -299,6 +368,22 @@ class RefScene:
     def replay(self, cam, W, H):
         """One sample per pixel on the oracle's draws (ref_driver.cpp: replay_frame): (H, W, 3)."""
         return self._frames("replay", cam, W, H).reshape(H, W, 3)
+
+    def replay_log(self, cam, W, H, log):
+        """Scene::adaptiveSampleScene per pixel with the pool laid out from the oracle's draw log
+        (OracleScene.render(..., draw_log=True); ref_driver.cpp: replay_log_frame), every chain
+        level, path and eye ray: dict of rgb (H, W, 3) float32, rgb8 (H, W, 3) uint8 as
+        Image::setPixel stored it, consumed (H, W) uint32 draws the reference took."""
+        off, keys = np.asarray(log["draw_offsets"], np.int64), np.ascontiguousarray(log["draw_keys"], "<u4")
+        assert len(off) == W * H + 1 and keys.shape == (int(off[-1]), 2)
+        out = self._out()
+        _run(["replaylog", self._scene_file(cam, W, H), self._blob(np.diff(off).astype("<u4"), keys), out])
+        raw = open(out, "rb").read()
+        n = W * H
+        assert len(raw) == n * 12 + n * 3 + n * 4
+        return {"rgb": np.frombuffer(raw, "<f4", n * 3).reshape(H, W, 3).copy(),
+                "rgb8": np.frombuffer(raw, np.uint8, n * 3, n * 12).reshape(H, W, 3).copy(),
+                "consumed": np.frombuffer(raw, "<u4", n, n * 15).reshape(H, W).copy()}
 
     def repeat(self, cam, W, H, K):
         """K renders in one process, the RNG stream running on: (K, H, W, 3) independent replicas."""

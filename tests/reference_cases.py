@@ -220,6 +220,150 @@ def replay_cases():
     return c
 
 
+def sphere(radius, centre):
+    """sphere2.obj (closed, 960 triangles, shared normals) as mesh arrays, scaled about its own
+    centre to `radius` and moved to `centre`."""
+    def load():
+        s = O.OracleScene()
+        return s.mesh_arrays(s.add_obj(ref_model("sphere2.obj"), s.add_material("lambert")))
+    v, n, vi, ni = _once("sphere2", load)
+    c = (v.min(0) + v.max(0)) * np.float32(0.5)
+    r = np.float32((v.max(0) - v.min(0)).max() * 0.5)
+    return ((v - c) * (np.float32(radius) / r) + np.asarray(centre, np.float32)).astype(np.float32), n, vi, ni
+
+
+def room(lo=(0.0, 0.0, -5.5), hi=(5.5, 5.5, 0.0)):
+    """A closed box of six quads, every normal pointing inwards; (verts, normals, vidx, nidx)."""
+    V, N, F, NI = [], [], [], []
+    for axis in range(3):
+        for side in (0, 1):
+            a, b = (axis + 1) % 3, (axis + 2) % 3
+            q = []
+            for da, db in ((0, 0), (1, 0), (1, 1), (0, 1)):
+                p = [0.0, 0.0, 0.0]
+                p[axis] = (lo, hi)[side][axis]; p[a] = (lo, hi)[da][a]; p[b] = (lo, hi)[db][b]
+                q.append(p)
+            n = [0.0, 0.0, 0.0]
+            n[axis] = -1.0 if side else 1.0
+            k = len(V)
+            V += q; N.append(n)
+            F += [(k, k + 2, k + 1), (k, k + 3, k + 2)] if side else [(k, k + 1, k + 2), (k, k + 2, k + 3)]   # wound to face inwards too
+            NI += [(len(N) - 1,) * 3] * 2
+    return np.array(V, np.float32), np.array(N, np.float32), np.array(F, np.uint32), np.array(NI, np.uint32)
+
+
+def corner():
+    """Three large quads in the open: a floor and two walls meeting in a corner; (verts, normals, vidx, nidx)."""
+    V = np.array([(0, 0, 0), (6, 0, 0), (6, 0, -6), (0, 0, -6),          # floor, +y
+                  (0, 0, -6), (6, 0, -6), (6, 5, -6), (0, 5, -6),        # back wall, +z
+                  (0, 0, 0), (0, 0, -6), (0, 5, -6), (0, 5, 0)], np.float32)   # left wall, +x
+    N = np.array([(0, 1, 0), (0, 0, 1), (1, 0, 0)], np.float32)
+    F = np.array([(0, 1, 2), (0, 2, 3), (4, 5, 6), (4, 6, 7), (8, 9, 10), (8, 10, 11)], np.uint32)
+    return V, N, F, np.repeat(np.arange(3, dtype=np.uint32), 2)[:, None].repeat(3, 1)
+
+
+# A Blinn whose Fresnel term is large at every angle (ior 50: Rs = 0.92 head-on), so that reflectAmt
+# decides how often a reflection ray goes out, and chains last.  The roulette draws twice (leave direct
+# light, then take the reflection), so that is with probability (reflectAmt * Rs) squared.
+MIRROR = dict(kind="blinn", kd=(0.7, 0.7, 0.7), specExp=20.0, specAmt=0.3, reflectAmt=0.9, refractAmt=0.0, ior=50.0)
+GLASS = _glass(0.3, 0.9)
+DEEP_CAM = dict(eye=(2.75, 2.75, 6.0), lookAt=(2.75, 2.75, 0.0), up=(0, 1, 0), fov=32.0)
+SPHERE_ROW = [((2.75, 2.75, 2.2), 1.0), ((2.75, 2.75, -0.6), 1.2), ((2.75, 2.75, -3.6), 1.4)]
+
+
+def deep_cases():
+    """name -> case whose chains go past level 0: the reference runs Scene::adaptiveSampleScene on
+    the oracle's logged draws (ref_driver replaylog), every level, path and eye ray.  Each puts one
+    piece of Blinn::shade at level >= 1 (tests/test_reference_cpu.py asserts, from the oracle's
+    log alone, that it gets there).  Lambert never recurses, so what carries a chain is a Blinn.
+    The cases keep to DESIGN.md section 7's traps: every light here casts fast shadows, so no
+    transparent shadow walk meets a Lambert; no case uses a normal map; emitters are set through
+    the setters; and a wall that must reflect faces the ray (mirror_box)."""
+    c = {}
+    rect1 = dict(RECT, samples=1)
+    # a closed room whose six walls all face inwards (a wall seen from behind pops the ray's IOR history
+    # and the Fresnel term falls to nothing): no reflection leaves it, and every hit reflects alike
+    walls = dict(MIRROR, reflectAmt=0.6, ior=1000.0)
+    c["mirror_box"] = dict(cfg=dict(C1, material=walls), meshes=[room()],
+                           camera=dict(eye=(2.6, 2.9, -0.3), lookAt=(2.2, 2.4, -5.5), up=(0, 1, 0), fov=70.0))
+    # three spheres in a row along the view axis: in, out, in, out, in, out is level 5
+    row = [(sphere(r, p), GLASS) for p, r in SPHERE_ROW]
+    c["glass_sphere"] = dict(_box(), lights=[rect1], extra=row, camera=DEEP_CAM)
+    c["glass_in_glass"] = dict(_box(), lights=[rect1], camera=DEEP_CAM,
+                               extra=[(sphere(1.7, (2.75, 2.75, 0.5)), GLASS),
+                                      (sphere(0.9, (2.75, 2.75, 0.5)), dict(GLASS, ior=1.8))])
+    glossy = dict(MIRROR, specGloss=0.8)
+    c["glossy_rect"] = dict(_box(glossy), lights=[dict(RECT, samples=4, noise=0.05)])
+    c["dispersion_sphere"] = dict(_box(), lights=[rect1], camera=DEEP_CAM,
+                                  extra=[(sphere(1.5, (2.75, 2.75, 1.0)), _glass(0.3, 0.9, disperse=True, ior3=(1.45, 1.5, 1.6)))])
+    img, typ = leaf_image()
+    c["translucent_behind_mirror"] = dict(
+        _box(MIRROR), lights=[dict(RECT, samples=2)], camera=FLOOR_CAM,
+        extra=[(quads(), dict(kind="blinn", kd=(1, 1, 1), translucency=0.4, maps=dict(color=(img, typ))))])
+    maps = synthetic_maps()
+    grey = lambda seed: (np.random.default_rng(seed).uniform(0.2, 1.0, (48, 64)).astype(np.float32), TEX_GRAY)  # noqa: E731
+    c["reflect_refract_maps"] = dict(
+        _box(MIRROR), lights=[rect1],
+        extra=[(quads(), dict(_glass(0.9, 0.9), maps=dict(color=maps["color"], reflect=grey(21), refract=grey(22))))])
+    matte = dict(kind="blinn", kd=(0.8, 0.8, 0.8))
+    emitter = dict(kind="blinn", kd=(1, 1, 1), emitted=2.0, le=(1.0, 0.9, 0.7))
+    c["path_trace_3"] = dict(_box(matte), path_trace=(3, False), lights=[dict(RECT, samples=2)],
+                             extra=[(quads()[:4], emitter)])
+    c["path_trace_env"] = dict(cfg=dict(C1, material=matte, env=dict(sky="Arches_E_PineTree.hdr", exposure=1.3)),
+                               meshes=[corner()], path_trace=(3, True), lights=[rect1],
+                               extra=[(quads(3, seed=2)[:4], matte)],
+                               camera=dict(eye=(5.5, 4.0, 0.5), lookAt=(1.5, 0.5, -4.0), up=(0, 1, 0), fov=50.0))
+    # the eye inside the first sphere: every camera ray meets a back face at level 0, where Blinn::shade
+    # pops the camera ray's own IOR history, and the four paths share that ray (src/Scene.cpp:228-231)
+    c["num_paths_4"] = dict(c["glass_sphere"], num_paths=4, camera=dict(DEEP_CAM, eye=(2.75, 2.75, 2.2), fov=60.0))
+    c["supersampled_dof"] = dict(c["glossy_rect"], subdivs=(1, 3, 0.01),
+                                 camera=dict(eye=(2.75, 2.75, 9.0), lookAt=(2.75, 2.75, 0.0), up=(0, 1, 0), fov=55.0,
+                                             aperture=0.3, focusPlane=11.0))
+    ground, ball, v2 = cannonball_parts()
+    # a mirror ceiling over the ground: the two reflect each other, and the moving ball, for as long as a chain lasts
+    lid = (np.array([(-3, 1.0, -3), (3, 1.0, -3), (3, 1.0, 3), (-3, 1.0, 3)], np.float32), np.array([(0, -1, 0)], np.float32),
+           np.array([(0, 1, 2), (0, 2, 3)], np.uint32), np.zeros((2, 3), np.uint32))
+    c["motion_blur_mirror"] = dict(cfg=dict(BALL_CFG, material=MIRROR), meshes=[ground], moving=[(ball, v2, MIRROR)],
+                                   extra=[(lid, MIRROR)], lights=[dict(type="point", pos=(1.0, 0.8, 1.0), power=8.0)],
+                                   camera=dict(BALL_CAM, shutterSpeed=0.6))
+    c["instanced_glass"] = dict(cfg=dict(C1, material=GLASS), lights=[rect1],
+                                instances=([ref_model("sphere2.obj")], [(0, M) for M in placements()]),
+                                extra=[(fixture_mesh("cornell_box"), LAMBERT)], camera=dict(CAM, fov=40.0))
+    return c
+
+
+def decode_key(keys):
+    """A draw log's (skey, dim) pairs as columns (sample, path, level, branch, k); camera draws are level -1."""
+    keys = np.asarray(keys, np.uint32).reshape(-1, 2).astype(np.int64)
+    skey, dim = keys[:, 0], keys[:, 1]
+    return np.stack([skey // 1024, skey % 1024, (dim >> 24) - 1, (dim >> 16) & 0xFF, dim & 0xFFFF], 1)
+
+
+# images whose decoding the reference's own loader is asked for (RawImage::loadImage)
+def decode_images():
+    from miro import final_scene
+    out = {name: ref_hdr_images()[name] for name in HDRS}
+    out["Tree_03_Leaves.tga"] = LEAF_TGA
+    for name in ("bw2.tga", "petal-pink-02.tga"):
+        out[name] = final_scene.asset(name)
+    return out
+
+
+def oracle_decode(path):
+    return O.hdr_load(path) if path.lower().endswith(".hdr") else O.image_load(path)[0]
+
+
+def map_inputs():
+    """The floats Map() is compared on: 0, the smallest normal, k / 32768 for a seeded sample of
+    512 k with one ulp either side, 1, 1 + ulp, 4 and 1e30.  No negative and no NaN inputs: the
+    reference's cast is undefined there and the oracle documents its deviation."""
+    k = np.sort(np.random.default_rng(168).choice(np.arange(1, 32768), 512, replace=False))
+    x = (k / 32768.0).astype(np.float32)
+    one = np.float32(1.0)
+    return np.concatenate([np.array([0.0, np.finfo(np.float32).tiny], np.float32), _ulp(x, -1), x, _ulp(x, 1),
+                           np.array([one, np.nextafter(one, np.float32(2.0)), 4.0, 1e30], np.float32)]).astype(np.float32)
+
+
 STAT_K = 64
 STAT_SIZE = (32, 32)
 

@@ -13,9 +13,14 @@ oracle/refdriver.py on the cases of tests/reference_cases.py:
                     equal counts on every ray pin the tree and the order it is walked in),
                     deterministic shading, and stochastic shading with the oracle's draws
                     replayed through the reference's random-number pool;
-  statistical tier  what spans chain levels (the draw keys change there and replay does not
-                    reach): the oracle's frame against the reference's distribution over 64
-                    replicas.
+  deep tier         uint32 bits at every chain level, path and eye ray: the oracle logs the key of
+                    every draw it takes, in call order; the driver lays oro_rand of those keys into
+                    the reference's pool, NaN after them, and runs the whole of
+                    Scene::adaptiveSampleScene.  Frames, 8-bit pixels and the number of draws the
+                    reference consumed per pixel must all be the oracle's.  Also the two gamma
+                    tables, Map() and RawImage's decoders;
+  statistical tier  the oracle's frame against the reference's distribution over 64 replicas:
+                    what a single replayed frame cannot show (behaviour across many paths).
 
 Two halves.  The live half needs the driver and skips without it (only where the reference's
 sources exist must the driver exist: test_driver_built_where_reference_exists).  The recorded
@@ -45,6 +50,7 @@ live = pytest.mark.skipif(not refdriver.available(), reason="oracle/_ref/ref_dri
 DET = RC.deterministic_cases()
 REPLAY = RC.replay_cases()
 STAT = RC.statistical_cases()
+DEEP = RC.deep_cases()
 
 
 def test_driver_built_where_reference_exists():
@@ -250,3 +256,173 @@ def test_z_bound_is_the_t_distribution_tail():
     assert abs(RC.t_two_sided_tail(2.0, 63) - 0.0498) < 2e-4
     b = RC.z_bound(3072, 63)
     assert 5.5 < b < 6.0 and abs(3072 * RC.t_two_sided_tail(b, 63) - 1e-3) < 1e-6
+
+
+# ------------------------------------------------------------------ deep tier: every chain level, replayed
+_logged = {}
+
+
+def deep_log(name):
+    """The oracle's frame of a deep case with its draw log, rendered once and left unchanged."""
+    if name not in _logged:
+        case = DEEP[name]
+        Os, _ = RC.build_scenes(case, False)
+        _logged[name] = Os.render(RC.case_camera(case), *RC.case_size(case), threads=4, draw_log=True)
+        for a in _logged[name].values():
+            a.setflags(write=False)
+    return _logged[name]
+
+
+def pixel_of_draws(log):
+    return np.repeat(np.arange(len(log["draw_offsets"]) - 1), np.diff(log["draw_offsets"]))
+
+
+def explain(name, log, rgb, rgb8, draws):
+    """None if the oracle's logged frame has these float bits, bytes and per-pixel draw counts; else
+    the first differing pixel and its log decoded as (sample, path, level, branch, k)."""
+    h, w = log["rgb"].shape[:2]
+    n = np.diff(log["draw_offsets"]).reshape(h, w)
+    bad = (bits(log["rgb"]) != bits(rgb)).any(2) | (log["rgb8"] != rgb8).any(2) | (n != draws)
+    if not bad.any():
+        return None
+    y, x = (int(v) for v in np.argwhere(bad)[0])
+    p = y * w + x
+    keys = log["draw_keys"][log["draw_offsets"][p]:log["draw_offsets"][p + 1]]
+    return "%s: %d pixels differ; first (x %d, y %d): oracle %r %r draws %d, reference %r %r draws %d; " \
+           "log (sample, path, level, branch, k): %r" % (
+               name, int(bad.sum()), x, y, log["rgb"][y, x].tolist(), log["rgb8"][y, x].tolist(), int(n[y, x]),
+               np.asarray(rgb)[y, x].tolist(), np.asarray(rgb8)[y, x].tolist(), int(draws[y, x]), RC.decode_key(keys).tolist())
+
+
+@live
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_replay_matches_the_reference(name):
+    """Float bits of the frame, the bytes Image::setPixel stored, and consumed == logged on every pixel."""
+    case, log = DEEP[name], deep_log(name)
+    _, Rs = RC.build_scenes(case, True)
+    w, h = RC.case_size(case)
+    ref = Rs.replay_log(RC.case_camera(case), w, h, log)
+    Rs.close()
+    why = explain(name, log, ref["rgb"], ref["rgb8"], ref["consumed"])
+    assert why is None, why
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_replay_matches_the_recorded_reference(name):
+    """Without the driver: the recorded frame, bytes and draw counts.  The oracle's log length of each
+    pixel equals the number of draws the reference consumed there."""
+    fx, log = RC.fixture("deep.npz"), deep_log(name)
+    w, h = RC.case_size(DEEP[name])
+    ref = fx[name + ".rgb"]
+    assert ref.shape == (h, w, 3) and w <= 40 and h <= 36
+    assert np.isfinite(ref).all() and np.unique(bits(ref)).size > 20
+    meta = RC.fixture_json()["deep"]["frames"][name]
+    assert RC.sha(ref) == meta["sha256"] and int(fx[name + ".draws"].max()) == meta["max_draws"]
+    why = explain(name, log, ref, fx[name + ".rgb8"], fx[name + ".draws"].astype(np.int64))
+    assert why is None, why
+
+
+def test_recorded_deep_frames_are_the_cases_of_the_table():
+    fx = RC.fixture("deep.npz")
+    want = {n + s for n in DEEP for s in (".rgb", ".rgb8", ".draws")} | {"gamma.u8", "gamma.f32", "map.in", "map.out"}
+    assert set(fx) == want and set(RC.fixture_json()["deep"]["frames"]) == set(DEEP)
+    assert set(RC.fixture_json()["deep"]["decode"]) == set(RC.decode_images())
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_draw_log_leaves_the_frame_alone(name):
+    """The log records; it takes no part in the arithmetic.  With any thread count (each pixel logs
+    into storage of its own) the frame has the bits of the frame rendered without it."""
+    case, log = DEEP[name], deep_log(name)
+    Os, _ = RC.build_scenes(case, False)
+    w, h = RC.case_size(case)
+    plain = Os.render(RC.case_camera(case), w, h, threads=1)
+    assert same_bits(plain["rgb"], log["rgb"]) and np.array_equal(plain["rgb8"], log["rgb8"])
+    one = Os.render(RC.case_camera(case), w, h, threads=1, draw_log=True)
+    assert np.array_equal(one["draw_keys"], log["draw_keys"]) and np.array_equal(one["draw_offsets"], log["draw_offsets"])
+    assert len(log["draw_keys"]) == log["draw_offsets"][-1]
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_cases_reach_past_level_one(name):
+    """From the oracle's log alone: level = (dim >> 24) - 1.  At least a tenth of the pixels draw at
+    level >= 2, and no pixel comes near the 65536 draws at which the reference's pool wraps."""
+    log = deep_log(name)
+    d, pix = RC.decode_key(log["draw_keys"]), pixel_of_draws(log)
+    n_pix = len(log["draw_offsets"]) - 1
+    assert np.unique(pix[d[:, 2] >= 2]).size >= 0.10 * n_pix
+    assert np.diff(log["draw_offsets"]).max() < 65536
+
+
+def test_deep_cases_do_what_their_names_say():
+    def parts(name):
+        log = deep_log(name)
+        return log, RC.decode_key(log["draw_keys"]), pixel_of_draws(log), len(log["draw_offsets"]) - 1
+    for name in ("mirror_box", "glass_sphere"):      # the bounces < 5 cap is reached
+        _, d, _, _ = parts(name)
+        assert d[:, 2].max() == 5, name
+    assert deep_log("glass_in_glass")["max_ior"].max() >= 3       # 1, 1.001, outer glass, inner glass
+    log, d, pix, n_pix = parts("dispersion_sphere")
+    per_branch = [np.unique(pix[d[:, 3] == b]) for b in (1, 2, 3)]
+    assert np.intersect1d(np.intersect1d(per_branch[0], per_branch[1]), per_branch[2]).size >= 0.05 * n_pix
+    log, d, pix, n_pix = parts("glossy_rect")
+    assert np.unique(np.diff(log["draw_offsets"])).size >= 10
+    # path tracing: a level's light draws come after its child's draws
+    log, d, pix, n_pix = parts("path_trace_3")
+    back = (pix[1:] == pix[:-1]) & (d[1:, 2] >= 0) & (d[1:, 2] + 1 == d[:-1, 2])
+    assert np.unique(pix[1:][back]).size >= 0.10 * n_pix
+    log, d, pix, n_pix = parts("num_paths_4")
+    assert set(d[:, 1]) == {0, 1, 2, 3}
+    assert not same_bits(log["rgb"], oracle_frame(dict(DEEP["num_paths_4"], num_paths=1)))
+    # supersampling: 1 + 4 eye rays where the first level settles the pixel, 1 + 4 + 9 elsewhere; the lens
+    # rejection loop (two draws a try after the three of jitter and time) takes a varying number of tries
+    log, d, pix, n_pix = parts("supersampled_dof")
+    eyes = np.array([np.unique(d[a:b, 0]).size for a, b in zip(log["draw_offsets"][:-1], log["draw_offsets"][1:])])
+    assert set(eyes) == {5, 14} and (eyes == 5).sum() >= 10 and (eyes == 14).sum() >= 10
+    cam = d[d[:, 2] == -1]
+    per_ray = np.unique(np.stack([pix[d[:, 2] == -1], cam[:, 0]], 1), axis=0, return_counts=True)[1]
+    assert ((per_ray - 3) % 2 == 0).all() and ((per_ray - 3) // 2).min() == 1 and ((per_ray - 3) // 2).max() >= 3
+
+
+# ------------------------------------------------------------------ gamma tables, Map(), decoders
+def check_gamma_and_map(u8, f32, x, mapped):
+    assert u8.shape == (32769,) and f32.shape == (32769,)
+    assert np.array_equal(O.gamma_table(), u8) and same_bits(O.gamma_table_f(), f32)
+    assert np.array_equal(O.map_channel(x), mapped)
+
+
+def test_map_inputs_are_the_listed_values():
+    x = RC.map_inputs()
+    assert len(x) == 2 + 3 * 512 + 4 and x[0] == 0 and x[1] == np.finfo(np.float32).tiny
+    assert list(x[-4:]) == [1.0, np.nextafter(np.float32(1), np.float32(2)), 4.0, np.float32(1e30)]
+    assert (x >= 0).all() and not np.isnan(x).any()
+    k = x[2 + 512:2 + 1024] * 32768
+    assert (k == np.round(k)).all() and np.unique(k).size == 512
+    assert np.array_equal(bits(x[2:514]) + 1, bits(x[514:1026])) and np.array_equal(bits(x[514:1026]) + 1, bits(x[1026:1538]))
+
+
+@live
+def test_gamma_tables_and_map_match_the_reference():
+    u8, f32 = refdriver.gamma_tables()
+    x = RC.map_inputs()
+    check_gamma_and_map(u8, f32, x, refdriver.map_values(x))
+
+
+def test_gamma_tables_and_map_match_the_recorded_reference():
+    fx = RC.fixture("deep.npz")
+    assert same_bits(fx["map.in"], RC.map_inputs())
+    check_gamma_and_map(fx["gamma.u8"], fx["gamma.f32"], fx["map.in"], fx["map.out"])
+
+
+@live
+@pytest.mark.parametrize("name", sorted(RC.decode_images()))
+def test_decoder_matches_the_reference(name):
+    path = RC.decode_images()[name]
+    ours, theirs = RC.oracle_decode(path), refdriver.decode(path)
+    assert ours.shape == theirs.shape and same_bits(ours, theirs)
+
+
+@pytest.mark.parametrize("name", sorted(RC.decode_images()))
+def test_decoder_matches_the_recorded_reference(name):
+    ours, rec = RC.oracle_decode(RC.decode_images()[name]), RC.fixture_json()["deep"]["decode"][name]
+    assert list(ours.shape) == rec["shape"] and RC.sha(ours) == rec["sha256"]

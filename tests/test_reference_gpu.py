@@ -4,21 +4,24 @@ tests/golden/reference/ holds what the reference's own code computed for the cas
 tests/reference_cases.py (oracle/ref/make_reference_fixtures.py wrote it from
 oracle/_ref/ref_driver; tests/test_reference_cpu.py holds the oracle to the same files).
 Here the same cases go through the C ABI and miro on the GPU and are compared with those
-files, not with the oracle: bits for the exact tier, the three statistical assertions for
-the frames that span chain levels.  Nothing here needs the reference or its driver.
+files, not with the oracle: bits for the exact tier and for the deep tier (every chain level,
+path and eye ray, the reference run on the logged draws: float frame and 8-bit pixels), the
+three statistical assertions for the statistical tier.  Nothing here needs the reference or
+its driver.
 """
 import numpy as np
 import pytest
 
 import miro
 import reference_cases as RC
-from helpers import bits, camera, scene_pair
+from helpers import bits, camera, scene_pair, tuned
 
 pytestmark = pytest.mark.gpu
 
 DET = RC.deterministic_cases()
 REPLAY = RC.replay_cases()
 STAT = RC.statistical_cases()
+DEEP = RC.deep_cases()
 
 
 def product(case):
@@ -77,3 +80,52 @@ def test_distribution_matches_the_recorded_reference(name):
     print(name, "held-out", held, "device", ours)
     RC.assert_statistics(held, "the reference's held-out replica")
     RC.assert_statistics(ours, "the device")
+
+
+# ------------------------------------------------------------------ deep tier
+_products = {}
+
+
+def deep_product(name):
+    if name not in _products:
+        _products[name] = product(DEEP[name])
+    return _products[name]
+
+
+def assert_deep_frame(name):
+    fx = RC.fixture("deep.npz")
+    case = DEEP[name]
+    w, h = RC.case_size(case)
+    img = miro.Image(); img.resize(w, h)
+    P = deep_product(name)
+    P.raytraceImage(camera(RC.case_camera(case)), img)
+    ref = fx[name + ".rgb"]
+    bad = (bits(img.rgb) != bits(ref)).any(2)
+    assert img.rgb.shape == ref.shape and not bad.any(), (name, int(bad.sum()), np.argwhere(bad)[:1].tolist())
+    assert np.array_equal(img.pixels, fx[name + ".rgb8"])
+    return P
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_frame_matches_the_recorded_reference(name):
+    """raytraceImage's float frame and img.pixels against what Scene::adaptiveSampleScene and
+    Image::setPixel made of the same draws at every chain level."""
+    assert_deep_frame(name)
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_frame_in_chunks_matches_the_recorded_reference(name):
+    """The same under worst-case level capacities in a 1-MB scratch budget: the chunked route."""
+    with tuned(chain_mb=1, chain_est=0):
+        P = assert_deep_frame(name)
+    assert P.last_stats["chain_chunks"] > 1 and P.last_stats["secondary_rays"] > 0, P.last_stats
+
+
+@pytest.mark.parametrize("name", sorted(n for n in DEEP if "subdivs" not in DEEP[n]))
+def test_deep_sample_rays_matches_the_recorded_reference(name):
+    """One eye ray per pixel: mrt_sample_rays on mrt_camera_rays' rays is the same frame."""
+    case = DEEP[name]
+    w, h = RC.case_size(case)
+    o, d, t = camera(RC.case_camera(case)).rays(w, h)
+    rgb = deep_product(name).sampleRays(o, d, t)
+    assert np.array_equal(bits(rgb), bits(RC.fixture("deep.npz")[name + ".rgb"]))
