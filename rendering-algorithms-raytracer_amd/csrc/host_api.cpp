@@ -67,10 +67,38 @@ static const TuneRow* tune_row(const char* key) {
     return nullptr;
 }
 
+// What refit_check and deform_check share, `name` being the entry's in its messages: a built
+// scene and a mesh of it before the entry's own refusals ...
+static int mesh_check(const Scene& S, int mesh, const std::string& name) {
+    if (!S.built) { set_error(name + ": scene not built"); return MRT_ERR_NOT_BUILT; }
+    if (mesh < 0 || mesh >= (int)S.meshes.size()) { set_error(name + ": bad mesh id"); return MRT_ERR_INVALID; }
+    return MRT_OK;
+}
+// ... and after them a hierarchy of the build and finite arrays (verts == nullptr: the async
+// forms, whose arrays are on the device)
+static int arrays_check(const Scene& S, const Mesh& m, const std::string& name, const float* verts, const float* verts2,
+                        const float* normals) {
+    if (S.imported) {
+        set_error(name + ": the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
+        return MRT_ERR_INVALID;
+    }
+    auto finite = [&](const float* p, size_t n, const char* what) {
+        for (size_t i = 0; i < 3 * n; i++)
+            if (!std::isfinite(p[i])) {
+                set_error(name + ": " + what + " " + std::to_string(i / 3) + " is not finite");
+                return false;
+            }
+        return true;
+    };
+    if (verts && !finite(verts, m.verts.size(), "vertex")) return MRT_ERR_INVALID;
+    if (verts && verts2 && !finite(verts2, m.verts.size(), "motion vertex")) return MRT_ERR_INVALID;
+    if (verts && normals && !finite(normals, m.normals.size(), "normal")) return MRT_ERR_INVALID;
+    return MRT_OK;
+}
+
 // mrt_scene_update_mesh / _async (mrt_refit.hip): which scenes and meshes a refit takes
 int refit_check(const Scene& S, int mesh, const float* verts, const float* normals) {
-    if (!S.built) { set_error("update_mesh: scene not built"); return MRT_ERR_NOT_BUILT; }
-    if (mesh < 0 || mesh >= (int)S.meshes.size()) { set_error("update_mesh: bad mesh id"); return MRT_ERR_INVALID; }
+    if (const int rc = mesh_check(S, mesh, "update_mesh")) return rc;
     const Mesh& m = S.meshes[(size_t)mesh];
     if (S.mesh_blas[(size_t)mesh] >= 0) {
         set_error("update_mesh: the mesh belongs to a BLAS (an instanced mesh is not refitted: its instance boxes would move)");
@@ -80,21 +108,7 @@ int refit_check(const Scene& S, int mesh, const float* verts, const float* norma
         set_error("update_mesh: the mesh has motion vertices (mrt_scene_set_mesh_motion): an MBObject's box needs both sets");
         return MRT_ERR_INVALID;
     }
-    if (S.imported) {
-        set_error("update_mesh: the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
-        return MRT_ERR_INVALID;
-    }
-    auto finite = [&](const float* p, size_t n, const char* what) {
-        for (size_t i = 0; i < 3 * n; i++)
-            if (!std::isfinite(p[i])) {
-                set_error(std::string("update_mesh: ") + what + " " + std::to_string(i / 3) + " is not finite");
-                return false;
-            }
-        return true;
-    };
-    if (verts && !finite(verts, m.verts.size(), "vertex")) return MRT_ERR_INVALID;
-    if (normals && !finite(normals, m.normals.size(), "normal")) return MRT_ERR_INVALID;
-    return MRT_OK;
+    return arrays_check(S, m, "update_mesh", verts, nullptr, normals);
 }
 
 void refit_set_mesh(Mesh& m, const float* verts, const float* normals) {
@@ -107,8 +121,7 @@ void refit_set_mesh(Mesh& m, const float* verts, const float* normals) {
 // mrt_scene_deform_mesh / _async (mrt_refit.hip): which scenes, meshes and arrays it takes
 int deform_check(const Scene& S, int mesh, const float* verts, const float* verts2, bool has_verts2, const float* normals,
                  int* kind) {
-    if (!S.built) { set_error("deform_mesh: scene not built"); return MRT_ERR_NOT_BUILT; }
-    if (mesh < 0 || mesh >= (int)S.meshes.size()) { set_error("deform_mesh: bad mesh id"); return MRT_ERR_INVALID; }
+    if (const int rc = mesh_check(S, mesh, "deform_mesh")) return rc;
     const Mesh& m = S.meshes[(size_t)mesh];
     const bool in_blas = S.mesh_blas[(size_t)mesh] >= 0;
     if (in_blas && has_verts2) {
@@ -123,21 +136,7 @@ int deform_check(const Scene& S, int mesh, const float* verts, const float* vert
         set_error("deform_mesh: the mesh has motion vertices (mrt_scene_set_mesh_motion): give both sets, an MBObject's box needs them");
         return MRT_ERR_INVALID;
     }
-    if (S.imported) {
-        set_error("deform_mesh: the hierarchy was imported (mrt_scene_bvh_import) and need not be a tree: rebuild it");
-        return MRT_ERR_INVALID;
-    }
-    auto finite = [&](const float* p, size_t n, const char* what) {
-        for (size_t i = 0; i < 3 * n; i++)
-            if (!std::isfinite(p[i])) {
-                set_error(std::string("deform_mesh: ") + what + " " + std::to_string(i / 3) + " is not finite");
-                return false;
-            }
-        return true;
-    };
-    if (verts && !finite(verts, m.verts.size(), "vertex")) return MRT_ERR_INVALID;
-    if (verts && verts2 && !finite(verts2, m.verts.size(), "motion vertex")) return MRT_ERR_INVALID;
-    if (verts && normals && !finite(normals, m.normals.size(), "normal")) return MRT_ERR_INVALID;
+    if (const int rc = arrays_check(S, m, "deform_mesh", verts, verts2, normals)) return rc;
     *kind = in_blas ? kDeformBlas : has_verts2 ? kDeformMotion : kDeformWorld;
     return MRT_OK;
 }

@@ -1200,6 +1200,19 @@ int make_blas(Scene& s, const int32_t* meshes, int n_meshes, std::string& err) {
     return id;
 }
 
+namespace {
+// slot k of a node (SoA: min xyz, max xyz, four slots each) as a box, and back
+inline Box slot_box(const QNode& q, int k) {
+    return Box{{q.box[0 + k], q.box[4 + k], q.box[8 + k]}, {q.box[12 + k], q.box[16 + k], q.box[20 + k]}};
+}
+inline void store_slot(QNode& q, int k, const Box& b) {
+    for (int a = 0; a < 3; a++) {
+        q.box[4 * a + k] = b.mn[a];
+        q.box[12 + 4 * a + k] = b.mx[a];
+    }
+}
+}  // namespace
+
 // new ProxyObject(objects, bvh, M) with its ProxyMatrix (src/ProxyObject.cpp:5-12,
 // src/ProxyMatrix.cpp:3-8) and ProxyObject::getAABB (src/ProxyObject.cpp:45-72):
 // the BLAS root box (QBVH_Node::getAABB: the union of all four slots, unused ones
@@ -1224,7 +1237,7 @@ void instance_box(const QNode& r, const float* m16, float box[6]) {
     memcpy(M.m, m16, sizeof M.m);
     Box t = empty_box();
     for (int k = 0; k < 4; k++)
-        t = merge(t, Box{{r.box[0 + k], r.box[4 + k], r.box[8 + k]}, {r.box[12 + k], r.box[16 + k], r.box[20 + k]}});
+        t = merge(t, slot_box(r, k));
     const v3 P[8] = {mk(t.mn[0], t.mn[1], t.mx[2]), mk(t.mn[0], t.mx[1], t.mn[2]), mk(t.mx[0], t.mn[1], t.mn[2]),
                      mk(t.mn[0], t.mx[1], t.mx[2]), mk(t.mx[0], t.mx[1], t.mn[2]), mk(t.mx[0], t.mn[1], t.mx[2]),
                      mk(t.mn[0], t.mn[1], t.mn[2]), mk(t.mx[0], t.mx[1], t.mx[2])};
@@ -1256,9 +1269,6 @@ namespace {
 inline Box verts_box3(v3 A, v3 B, v3 C) {   // Builder::box3
     return Box{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
                {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
-}
-inline Box slot_box(const QNode& q, int k) {
-    return Box{{q.box[0 + k], q.box[4 + k], q.box[8 + k]}, {q.box[12 + k], q.box[16 + k], q.box[20 + k]}};
 }
 }  // namespace
 
@@ -1298,8 +1308,7 @@ void refit_nodes(std::vector<QNode>& nodes, const std::vector<Box>& lbox) {
                 for (int j = 0; j < 4; j++)
                     if (ch.child[j] != kEmptySlot) b = merge(b, slot_box(ch, j));
             }
-            q.box[0 + k] = b.mn[0]; q.box[4 + k] = b.mn[1]; q.box[8 + k] = b.mn[2];
-            q.box[12 + k] = b.mx[0]; q.box[16 + k] = b.mx[1]; q.box[20 + k] = b.mx[2];
+            store_slot(q, k, b);
         }
     }
 }
@@ -1312,42 +1321,33 @@ Box refit_lane(QLeaf& L, int i, const Mesh& m, int32_t tri) {
     L.t[24 + i] = C.x - A.x; L.t[28 + i] = C.y - A.y; L.t[32 + i] = C.z - A.z;
     return verts_box3(A, B, C);
 }
-}  // namespace
-
-void refit_host(Scene& s) {
-    std::vector<Box> lbox(s.leaves.size());
-    for (size_t li = 0; li < s.leaves.size(); li++) {
-        QLeaf& L = s.leaves[li];
+// One tree on the host: each packet's triangles from the vertices (obj_mesh / obj_tri: the
+// tree's own object tables) and its box, then the node boxes.  world: lanes that are
+// ProxyObjects or MBObjects (checkOut lanes: no triangle data) take the box of the object now.
+void refit_tree(const Scene& s, std::vector<QNode>& nodes, std::vector<QLeaf>& leaves, const std::vector<int32_t>& obj_mesh,
+                const std::vector<int32_t>& obj_tri, bool world) {
+    std::vector<Box> lbox(leaves.size());
+    for (size_t li = 0; li < leaves.size(); li++) {
+        QLeaf& L = leaves[li];
         Box b = empty_box();
         for (int i = 0; i < 4; i++) {
             const int32_t o = L.prim[i];
             if (o < 0) continue;
             float fb[6];
-            if (fixed_lane_box(s, o, fb)) {   // checkOut lanes: no triangle data, the box of the object now
-                b = merge(b, Box{{fb[0], fb[1], fb[2]}, {fb[3], fb[4], fb[5]}});
-                continue;
-            }
-            b = merge(b, refit_lane(L, i, s.meshes[(size_t)s.obj_mesh[(size_t)o]], s.obj_tri[(size_t)o]));
+            if (world && fixed_lane_box(s, o, fb)) b = merge(b, Box{{fb[0], fb[1], fb[2]}, {fb[3], fb[4], fb[5]}});
+            else b = merge(b, refit_lane(L, i, s.meshes[(size_t)obj_mesh[(size_t)o]], obj_tri[(size_t)o]));
         }
         lbox[li] = b;
     }
-    refit_nodes(s.nodes, lbox);
+    refit_nodes(nodes, lbox);
 }
+}  // namespace
+
+void refit_host(Scene& s) { refit_tree(s, s.nodes, s.leaves, s.obj_mesh, s.obj_tri, true); }
 
 void refit_blas_host(Scene& s, int32_t bi) {
     Blas& B = s.blas[(size_t)bi];
-    std::vector<Box> lbox(B.leaves.size());
-    for (size_t li = 0; li < B.leaves.size(); li++) {
-        QLeaf& L = B.leaves[li];
-        Box b = empty_box();
-        for (int i = 0; i < 4; i++) {
-            const int32_t o = L.prim[i];
-            if (o < 0) continue;
-            b = merge(b, refit_lane(L, i, s.meshes[(size_t)B.obj_mesh[(size_t)o]], B.obj_tri[(size_t)o]));
-        }
-        lbox[li] = b;
-    }
-    refit_nodes(B.nodes, lbox);
+    refit_tree(s, B.nodes, B.leaves, B.obj_mesh, B.obj_tri, false);
     for (Instance& I : s.instances)
         if (I.blas == bi) instance_box(B.nodes[0], I.m, I.box);
 }

@@ -169,6 +169,17 @@ struct ShareBuf {
 // (mrt_hit_surfaces: HitInfo::obj of a hit on the device).
 struct SurfaceGroup { int32_t start, mesh, tri0, step; };
 
+// One tree the refit walks, the world's or a BLAS's: where it lies in the replica's arrays (the
+// upload), and the schedule the first refit makes: its nodes in device numbers sorted by height.
+struct RefitTree {
+    uint32_t node_base = 0, n_nodes = 0;    // node_base is the root (BLAS nodes are not permuted; the world's are: node_perm)
+    uint32_t leaf_base = 0, n_leaves = 0;   // DLeaf packets leaf_base .. leaf_base + n_leaves - 1
+    int32_t shade_base = 0;                 // PrimShade of its object 0
+    bool fixed_lanes = false;               // the world: ProxyObject / MBObject lanes take their boxes from refit_fixed
+    const int32_t* order = nullptr;         // its part of DeviceState::refit_order
+    std::vector<uint32_t> off;              //   height h holds order[off[h] .. off[h + 1])
+};
+
 struct DeviceState {
     int device = -1;
     SurfaceGroup* sgroups = nullptr;   // built by the first mrt_hit_surfaces call on this replica (one of bufs)
@@ -213,14 +224,13 @@ struct DeviceState {
     std::atomic<int> lds_pick{-1};   // the last one-light frame ran the LDS top-node walk: 1 yes, 0 no, -1 none yet
     float bb_lo[3] = {0, 0, 0}, bb_hi[3] = {0, 0, 0};   // world root box (ray-binning origin cells)
     // refit (mrt_refit.hip): per mesh the first float4 of its slice of verts / normals, the
-    // world hierarchy's size and its canonical -> device node numbers (the LDS breadth-first
+    // world hierarchy and its canonical -> device node numbers (the LDS breadth-first
     // permutation; empty = identity); the rest is made by the first refit on this replica
     std::vector<uint32_t> vbase, nbase;
     std::vector<int32_t> node_perm;
-    uint32_t n_world_nodes = 0, n_world_leaves = 0;
+    RefitTree world;                      // nodes, packets and PrimShade records from 0
     bool refit_ready = false;
-    int32_t* refit_order = nullptr;       // world device node numbers sorted by height (one of bufs)
-    std::vector<uint32_t> refit_off;      //   height h holds refit_order[refit_off[h] .. refit_off[h + 1])
+    int32_t* refit_order = nullptr;       // device node numbers of the world, then of every BLAS, each sorted by height (one of bufs)
     float4* refit_lbox = nullptr;         // per packet, world then BLASes, by device packet number: box min xyz, max xyz (2 float4; one of bufs)
     float4* refit_fixed = nullptr;        // ProxyObject lanes' boxes by instance, then MBObject lanes' (2 float4 each)
     int32_t* refit_mbslot = nullptr;      //   per world prim: its MBObject box after the instances', -1 = none
@@ -228,19 +238,15 @@ struct DeviceState {
     float* refit_stage = nullptr;         // the synchronous entry's packed vertices / normals on the device
     size_t refit_stage_cap = 0;           //   floats
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
-    // mrt_scene_deform_mesh: where each BLAS lies in nodes / leaves / prims (the upload; BLAS
-    // nodes are not permuted, their child words hold device node and packet numbers), and the
-    // schedule the first refit makes: its nodes by height and the ids of its instances
+    // mrt_scene_deform_mesh: where each BLAS lies in nodes / leaves / prims (the upload; its
+    // child words hold device node and packet numbers), and what the first refit adds: its
+    // tree's schedule and the ids of its instances
     struct BlasRange {
-        uint32_t node_base = 0, n_nodes = 0, leaf_base = 0, n_leaves = 0;   // node_base is the root
-        int32_t shade_base = 0;                                             // PrimShade of its object 0
-        std::vector<uint32_t> off;         // height h holds refit_blas_order[order_at + off[h] .. order_at + off[h + 1])
-        uint32_t order_at = 0;
-        uint32_t inst_at = 0, n_inst = 0;  // refit_blas_insts[inst_at .. inst_at + n_inst): its instances, ascending
+        RefitTree tree;
+        uint32_t inst_at = 0, n_inst = 0;      // refit_blas_insts[inst_at .. inst_at + n_inst): its instances, ascending
     };
     std::vector<BlasRange> blas;
     uint32_t n_leaves_all = 0;             // packets of the world and every BLAS (refit_lbox holds them all)
-    int32_t* refit_blas_order = nullptr;   // device node numbers of every BLAS, each sorted by height (one of bufs)
     int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS (one of bufs)
     std::vector<int32_t> mesh_prim0;       // per mesh: its first world prim (its triangles follow in order), -1 = none
     int cus = 0;

@@ -11,6 +11,10 @@
 // kernels over that BLAS's range, one kernel that recomputes the box of each of its instances
 // from the refitted root, then the world tree.  A motion-blurred world mesh: both vertex sets,
 // one kernel that recomputes the union box of each of its MBObject lanes, then the world tree.
+// One pipeline serves them all: a RefitTree (mrt_device.h) is the world or a BLAS, with one
+// height_schedule, enqueue_tree and read_tree for either; enqueue_mesh is the launch sequence
+// of every mesh entry, refit_replicas the per-replica loop of every synchronous entry and
+// async_ready what every async entry asks of the scene.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -40,6 +44,30 @@ __device__ __forceinline__ DBox d_merge(const DBox& a, const DBox& b) {
         r.hi[k] = std_max(a.hi[k], b.hi[k]);
     }
     return r;
+}
+// slot k of a node (SoA: min xyz, max xyz, four slots each) as a box, and back
+__device__ __forceinline__ DBox d_slot_box(const QNode& q, int k) {
+    return DBox{{q.box[0 + k], q.box[4 + k], q.box[8 + k]}, {q.box[12 + k], q.box[16 + k], q.box[20 + k]}};
+}
+__device__ __forceinline__ void d_store_slot(QNode& q, int k, const DBox& b) {
+    q.box[0 + k] = b.lo[0]; q.box[4 + k] = b.lo[1]; q.box[8 + k] = b.lo[2];
+    q.box[12 + k] = b.hi[0]; q.box[16 + k] = b.hi[1]; q.box[20 + k] = b.hi[2];
+}
+// box i of the float4 pairs (min xyz, max xyz) in lbox and fixed, and back
+template <typename I>
+__device__ __forceinline__ DBox d_load_box(const float4* p, I i) {
+    const float4 lo = p[2 * i], hi = p[2 * i + 1];
+    return DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+}
+template <typename I>
+__device__ __forceinline__ void d_store_box(float4* p, I i, const DBox& b) {
+    p[2 * (size_t)i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
+    p[2 * (size_t)i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+}
+// Builder::box3 of a triangle's vertices
+__device__ __forceinline__ DBox d_tri_box(const float4 A, const float4 B, const float4 C) {
+    return DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
+                {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
 }
 
 // n packed (x, y, z) -> float4 (x, y, z, w) at dst (and dst2: the time-1 copy of a static mesh)
@@ -73,8 +101,7 @@ __global__ __launch_bounds__(kRefitWG) void refit_leaf_kernel(DLeaf* __restrict_
         if (prim <= -2) fx = -2 - prim;
         else if (prim >= 0 && pflags && (pflags[prim] & 1u)) fx = n_insts + mbslot[prim];
         if (fx >= 0) {
-            const float4 lo = fixed[2 * fx], hi = fixed[2 * fx + 1];
-            b = DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+            b = d_load_box(fixed, fx);
             used = 1;
         } else if (prim >= 0) {
             const PrimShade ps = prims[prim];
@@ -83,8 +110,7 @@ __global__ __launch_bounds__(kRefitWG) void refit_leaf_kernel(DLeaf* __restrict_
             t[0] = A.x; t[1] = A.y; t[2] = A.z;
             t[3] = B.x - A.x; t[4] = B.y - A.y; t[5] = B.z - A.z;
             t[6] = C.x - A.x; t[7] = C.y - A.y; t[8] = C.z - A.z;
-            b = DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
-                     {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
+            b = d_tri_box(A, B, C);
             used = 1;
         }
     }
@@ -98,10 +124,7 @@ __global__ __launch_bounds__(kRefitWG) void refit_leaf_kernel(DLeaf* __restrict_
         }
         if (__shfl(used, j, 4)) acc = d_merge(acc, o);
     }
-    if (in && k == 0) {
-        lbox[2 * (size_t)leaf] = make_float4(acc.lo[0], acc.lo[1], acc.lo[2], 0.f);
-        lbox[2 * (size_t)leaf + 1] = make_float4(acc.hi[0], acc.hi[1], acc.hi[2], 0.f);
-    }
+    if (in && k == 0) d_store_box(lbox, leaf, acc);
 }
 
 // One lane per slot of the n nodes of one height (order[0 .. n)): a leaf slot takes its
@@ -119,20 +142,14 @@ __global__ __launch_bounds__(kRefitWG) void refit_node_kernel(QNode* __restrict_
     if (c == kEmptySlot) return;
     DBox b;
     if (c < 0) {
-        const size_t leaf = (size_t)(~(uint32_t)c >> 4);   // leaf_child
-        const float4 lo = lbox[2 * leaf], hi = lbox[2 * leaf + 1];
-        b = DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+        b = d_load_box(lbox, (size_t)(~(uint32_t)c >> 4));   // leaf_child
     } else {
         const QNode* ch = nodes + c;
         b = d_empty_box();
-        for (int j = 0; j < 4; j++) {
-            if (ch->child[j] == kEmptySlot) continue;
-            const DBox o{{ch->box[0 + j], ch->box[4 + j], ch->box[8 + j]}, {ch->box[12 + j], ch->box[16 + j], ch->box[20 + j]}};
-            b = d_merge(b, o);
-        }
+        for (int j = 0; j < 4; j++)
+            if (ch->child[j] != kEmptySlot) b = d_merge(b, d_slot_box(*ch, j));
     }
-    q->box[0 + k] = b.lo[0]; q->box[4 + k] = b.lo[1]; q->box[8 + k] = b.lo[2];
-    q->box[12 + k] = b.hi[0]; q->box[16 + k] = b.hi[1]; q->box[20 + k] = b.hi[2];
+    d_store_slot(*q, (int)k, b);
 }
 
 // Matrix4x4::invert as inverse() of host_build.cpp states it, operation for operation: the 18
@@ -178,7 +195,7 @@ __device__ __forceinline__ float d_dp4(const float (&row)[4], float x, float y, 
 __device__ DBox d_instance_box(const float (&m)[4][4], const QNode& r, const uint16_t* __restrict__ rcpT) {
     DBox t = d_empty_box();
     for (int k = 0; k < 4; k++)
-        t = d_merge(t, DBox{{r.box[0 + k], r.box[4 + k], r.box[8 + k]}, {r.box[12 + k], r.box[16 + k], r.box[20 + k]}});
+        t = d_merge(t, d_slot_box(r, k));
     const float* lo = t.lo;
     const float* hi = t.hi;
     const float P[8][3] = {{lo[0], lo[1], hi[2]}, {lo[0], hi[1], lo[2]}, {hi[0], lo[1], lo[2]}, {lo[0], hi[1], hi[2]},
@@ -196,9 +213,7 @@ __device__ DBox d_instance_box(const float (&m)[4][4], const QNode& r, const uin
 // instance i's box from its matrix and its BLAS root, into the fixed boxes the leaf kernel reads
 __device__ __forceinline__ void d_fix_instance_box(float4* __restrict__ fixed, size_t i, const float (&m)[4][4],
                                                    const QNode& root, const uint16_t* __restrict__ rcpT) {
-    const DBox b = d_instance_box(m, root, rcpT);
-    fixed[2 * i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-    fixed[2 * i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+    d_store_box(fixed, i, d_instance_box(m, root, rcpT));
 }
 
 // ProxyMatrix::set for n instances, one lane each: lane g takes the row-major 4x4 at
@@ -264,15 +279,10 @@ __global__ __launch_bounds__(kRefitWG) void refit_motion_box_kernel(float4* __re
     const int32_t slot = mbslot[p];
     if (slot < 0) return;
     const PrimShade ps = prims[p];
-    auto box3 = [&](const float4* __restrict__ v) {
-        const float4 A = v[ps.v[0]], B = v[ps.v[1]], C = v[ps.v[2]];
-        return DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
-                    {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
-    };
+    auto box3 = [&](const float4* __restrict__ v) { return d_tri_box(v[ps.v[0]], v[ps.v[1]], v[ps.v[2]]); };
     const DBox b = d_merge(box3(verts), box3(verts2));
     const size_t f = (size_t)n_insts + (size_t)slot;
-    fixed[2 * f] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-    fixed[2 * f + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
+    d_store_box(fixed, f, b);
 }
 
 template <typename T>
@@ -283,40 +293,52 @@ int dev_array(DeviceState& d, T*& dst, const void* src, size_t bytes) {
     return MRT_OK;
 }
 
-// What the refit of replica d needs beyond the upload, made once (the topology never
-// changes while the replica lives): the node lists by height in device numbers, the packet
-// box scratch and the fixed boxes of ProxyObject / MBObject lanes.  The current device is d's.
-int prepare(const Scene& s, DeviceState& d) {
-    if (d.refit_ready) return MRT_OK;
-    const size_t nw = s.nodes.size();
-    if (nw != d.n_world_nodes || s.leaves.size() != d.n_world_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
-    // heights: every child has a larger canonical number than its parent (qbuild)
-    std::vector<int32_t> height(nw, 0);
+// The height schedule of tree T (`what` in the messages) from its canonical nodes N and n_leaves
+// packets: T.off by height and, appended to `order`, the nodes sorted by height in device
+// numbers (perm[i]; perm empty: T.node_base + i).  Every child has a larger canonical number
+// than its parent (qbuild).
+int height_schedule(const std::vector<QNode>& N, size_t n_leaves, const std::vector<int32_t>& perm, const char* what,
+                    RefitTree& T, std::vector<int32_t>& order) {
+    const size_t n = N.size();
+    if (n != T.n_nodes || n_leaves != T.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    std::vector<int32_t> height(n, 0);
     int32_t top = 0;
-    for (size_t i = nw; i-- > 0;) {
+    for (size_t i = n; i-- > 0;) {
         int32_t h = 0;
         for (int k = 0; k < 4; k++) {
-            const int32_t c = s.nodes[i].child[k];
+            const int32_t c = N[i].child[k];
             if (c < 0) continue;
-            if ((size_t)c <= i || (size_t)c >= nw) { set_error("refit: the hierarchy is not a tree in build order"); return MRT_ERR_INVALID; }
+            if ((size_t)c <= i || (size_t)c >= n) { set_error(std::string("refit: ") + what + " is not a tree in build order"); return MRT_ERR_INVALID; }
             h = std::max(h, height[(size_t)c] + 1);
         }
         height[i] = h;
         top = std::max(top, h);
     }
-    d.refit_off.assign((size_t)top + 2, 0);
-    for (size_t i = 0; i < nw; i++) d.refit_off[(size_t)height[i] + 1]++;
-    for (size_t h = 0; h + 1 < d.refit_off.size(); h++) d.refit_off[h + 1] += d.refit_off[h];
-    std::vector<int32_t> order(nw);
-    std::vector<uint32_t> at(d.refit_off.begin(), d.refit_off.end() - 1);
-    for (size_t i = 0; i < nw; i++) order[at[(size_t)height[i]]++] = d.node_perm.empty() ? (int32_t)i : d.node_perm[i];
+    T.off.assign((size_t)top + 2, 0);
+    for (size_t i = 0; i < n; i++) T.off[(size_t)height[i] + 1]++;
+    for (size_t h = 0; h + 1 < T.off.size(); h++) T.off[h + 1] += T.off[h];
+    const size_t first = order.size();
+    order.resize(first + n);
+    std::vector<uint32_t> at(T.off.begin(), T.off.end() - 1);
+    for (size_t i = 0; i < n; i++) order[first + at[(size_t)height[i]]++] = perm.empty() ? (int32_t)(T.node_base + i) : perm[i];
+    return MRT_OK;
+}
+
+// What the refit of replica d needs beyond the upload, made once (the topology never
+// changes while the replica lives): the node lists by height in device numbers, the packet
+// box scratch and the fixed boxes of ProxyObject / MBObject lanes.  The current device is d's.
+int prepare(const Scene& s, DeviceState& d) {
+    if (d.refit_ready) return MRT_OK;
+    int rc;
+    std::vector<int32_t> order;   // the world's nodes by height, then each BLAS's
+    if ((rc = height_schedule(s.nodes, s.leaves.size(), d.node_perm, "the hierarchy", d.world, order))) return rc;
     // fixed boxes: instance i at i, then the MBObject lanes
-    std::vector<float4> fixed(2 * s.instances.size());
-    for (size_t i = 0; i < s.instances.size(); i++) {
-        const float* b = s.instances[i].box;
-        fixed[2 * i] = make_float4(b[0], b[1], b[2], 0.f);
-        fixed[2 * i + 1] = make_float4(b[3], b[4], b[5], 0.f);
-    }
+    std::vector<float4> fixed;
+    auto push_box = [&](const float* b) {
+        fixed.push_back(make_float4(b[0], b[1], b[2], 0.f));
+        fixed.push_back(make_float4(b[3], b[4], b[5], 0.f));
+    };
+    for (const Instance& I : s.instances) push_box(I.box);
     std::vector<int32_t> mbslot;
     if (d.has_mb) {
         mbslot.assign(s.obj_mesh.size(), -1);
@@ -325,53 +347,34 @@ int prepare(const Scene& s, DeviceState& d) {
             float b[6];
             if (s.obj_inst[o] >= 0 || !fixed_lane_box(s, (int32_t)o, b)) continue;
             mbslot[o] = next++;
-            fixed.push_back(make_float4(b[0], b[1], b[2], 0.f));
-            fixed.push_back(make_float4(b[3], b[4], b[5], 0.f));
+            push_box(b);
         }
     }
-    int rc;
-    if ((rc = dev_array(d, d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_array(d, d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4)))) return rc;
-    if ((rc = dev_array(d, d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t)))) return rc;
     std::vector<float> inst_m(16 * s.instances.size());   // m_transform: the device keeps inv / inv_t only
     for (size_t i = 0; i < s.instances.size(); i++) memcpy(&inst_m[16 * i], s.instances[i].m, 16 * sizeof(float));
-    if ((rc = dev_array(d, d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float)))) return rc;
-    // each BLAS: its nodes by height in device numbers (node_base + canonical number: BLAS
-    // nodes are not permuted) and the ids of its instances; first prim of each world mesh
-    if (d.blas.size() != s.blas.size() || d.n_leaves_all < d.n_world_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
-    std::vector<int32_t> border, binsts;
+    // each BLAS: its nodes by height (BLAS nodes are not permuted) and the ids of its instances
+    if (d.blas.size() != s.blas.size() || d.n_leaves_all < d.world.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    std::vector<int32_t> binsts;
     for (size_t b = 0; b < s.blas.size(); b++) {
-        const std::vector<QNode>& BN = s.blas[b].nodes;
         DeviceState::BlasRange& R = d.blas[b];
-        if (BN.size() != R.n_nodes || s.blas[b].leaves.size() != R.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
-        std::vector<int32_t> bh(BN.size(), 0);
-        int32_t btop = 0;
-        for (size_t i = BN.size(); i-- > 0;) {
-            int32_t h = 0;
-            for (int k = 0; k < 4; k++) {
-                const int32_t c = BN[i].child[k];
-                if (c < 0) continue;
-                if ((size_t)c <= i || (size_t)c >= BN.size()) { set_error("refit: a BLAS hierarchy is not a tree in build order"); return MRT_ERR_INVALID; }
-                h = std::max(h, bh[(size_t)c] + 1);
-            }
-            bh[i] = h;
-            btop = std::max(btop, h);
-        }
-        R.off.assign((size_t)btop + 2, 0);
-        for (size_t i = 0; i < BN.size(); i++) R.off[(size_t)bh[i] + 1]++;
-        for (size_t h = 0; h + 1 < R.off.size(); h++) R.off[h + 1] += R.off[h];
-        R.order_at = (uint32_t)border.size();
-        border.resize(border.size() + BN.size());
-        std::vector<uint32_t> bat(R.off.begin(), R.off.end() - 1);
-        for (size_t i = 0; i < BN.size(); i++) border[R.order_at + bat[(size_t)bh[i]]++] = (int32_t)(R.node_base + i);
+        if ((rc = height_schedule(s.blas[b].nodes, s.blas[b].leaves.size(), {}, "a BLAS hierarchy", R.tree, order))) return rc;
         R.inst_at = (uint32_t)binsts.size();
         for (size_t i = 0; i < s.instances.size(); i++)
             if (s.instances[i].blas == (int32_t)b) binsts.push_back((int32_t)i);
         R.n_inst = (uint32_t)binsts.size() - R.inst_at;
     }
-    if ((rc = dev_array(d, d.refit_blas_order, border.data(), border.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_array(d, d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_array(d, d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4)))) return rc;
+    if ((rc = dev_array(d, d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_array(d, d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float)))) return rc;
     if ((rc = dev_array(d, d.refit_blas_insts, binsts.data(), binsts.size() * sizeof(int32_t)))) return rc;
-    d.mesh_prim0.assign(s.meshes.size(), -1);
+    d.world.order = d.refit_order;   // each tree's part of the one list
+    const int32_t* at = d.refit_order + d.world.n_nodes;
+    for (DeviceState::BlasRange& R : d.blas) {
+        R.tree.order = at;
+        at += R.tree.n_nodes;
+    }
+    d.mesh_prim0.assign(s.meshes.size(), -1);   // first prim of each world mesh
     for (size_t o = s.obj_mesh.size(); o-- > 0;)
         if (s.obj_mesh[o] >= 0) d.mesh_prim0[(size_t)s.obj_mesh[o]] = (int32_t)o;
     // the packet boxes of the world and of every BLAS, by device packet number (the child words' own)
@@ -385,35 +388,29 @@ int prepare(const Scene& s, DeviceState& d) {
 
 inline dim3 blocks(size_t n) { return dim3((unsigned)((n + kRefitWG - 1) / kRefitWG)); }
 
-// Enqueue on `stream`: the leaf kernel over the world packets and the node kernels, deepest
-// height first.
-int enqueue_tree(DeviceState& d, hipStream_t stream) {
-    const uint32_t n_lanes = 4u * d.n_world_leaves;
+// Enqueue on `stream`: tree T refitted to the vertices (and, the world, the fixed boxes) the
+// device holds now: the leaf kernel over its packets, then the node kernels, deepest height first.
+void enqueue_tree(DeviceState& d, const RefitTree& T, hipStream_t stream) {
+    const uint32_t n_lanes = 4u * T.n_leaves;
     if (n_lanes)
-        hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves, n_lanes, d.prims,
-                           d.verts, d.has_mb ? d.pflags : (uint8_t*)nullptr, d.refit_mbslot, d.refit_fixed, d.n_insts,
-                           d.refit_lbox);
-    for (size_t h = 0; h + 1 < d.refit_off.size(); h++) {
-        const uint32_t n = d.refit_off[h + 1] - d.refit_off[h];
+        hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves + T.leaf_base, n_lanes,
+                           (const PrimShade*)(d.prims + T.shade_base), (const float4*)d.verts,
+                           (const uint8_t*)(T.fixed_lanes && d.has_mb ? d.pflags : nullptr),
+                           (const int32_t*)(T.fixed_lanes ? d.refit_mbslot : nullptr), (const float4*)d.refit_fixed,
+                           d.n_insts, d.refit_lbox + 2 * (size_t)T.leaf_base);
+    for (size_t h = 0; h + 1 < T.off.size(); h++) {
+        const uint32_t n = T.off[h + 1] - T.off[h];
         if (!n) continue;
-        hipLaunchKernelGGL(refit_node_kernel, blocks((size_t)4 * n), dim3(kRefitWG), 0, stream, d.nodes,
-                           d.refit_order + d.refit_off[h], n, d.refit_lbox);
+        hipLaunchKernelGGL(refit_node_kernel, blocks((size_t)4 * n), dim3(kRefitWG), 0, stream, d.nodes, T.order + T.off[h],
+                           n, (const float4*)d.refit_lbox);
     }
-    HIP_OK(hipGetLastError());
-    return MRT_OK;
 }
 
-// Enqueue on `stream`: scatter nv vertices (and nn normals) from packed device arrays into
-// mesh m's slices, then the tree.
-int enqueue(DeviceState& d, int m, const float* d_verts, uint32_t nv, const float* d_normals, uint32_t nn,
-            hipStream_t stream) {
-    if (nv)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
-                           d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
-    if (d_normals && nn)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
-                           (float4*)nullptr, d_normals, nn, 0.f);
-    return enqueue_tree(d, stream);
+// the world tree, last in every entry's sequence: a launch that failed shows here
+int enqueue_world(DeviceState& d, hipStream_t stream) {
+    enqueue_tree(d, d.world, stream);
+    HIP_OK(hipGetLastError());
+    return MRT_OK;
 }
 
 // Enqueue on `stream`: n matrices (device, row-major 4x4 each) for the instances d_ids[0 .. n)
@@ -423,56 +420,38 @@ int enqueue_instances(DeviceState& d, const float* d_m16s, const int32_t* d_ids,
     if (n)
         hipLaunchKernelGGL(refit_instance_kernel, blocks(n), dim3(kRefitWG), 0, stream, d.insts, d.refit_inst_m,
                            d.refit_fixed, (const QNode*)d.nodes, (const uint16_t*)d.tables, d_m16s, d_ids, first, n);
-    return enqueue_tree(d, stream);
+    return enqueue_world(d, stream);
 }
 
-// Enqueue on `stream`: BLAS b refitted to the vertices the device holds now: the leaf kernel
-// over its packets (its PrimShade records start at shade_base; a BLAS has no fixed lanes), its
-// node kernels deepest height first, then the boxes of its instances.
-int enqueue_blas(DeviceState& d, int b, hipStream_t stream) {
-    const DeviceState::BlasRange& R = d.blas[(size_t)b];
-    const uint32_t n_lanes = 4u * R.n_leaves;
-    if (n_lanes)
-        hipLaunchKernelGGL(refit_leaf_kernel, blocks(n_lanes), dim3(kRefitWG), 0, stream, d.leaves + R.leaf_base, n_lanes,
-                           (const PrimShade*)(d.prims + R.shade_base), (const float4*)d.verts, (const uint8_t*)nullptr,
-                           (const int32_t*)nullptr, (const float4*)d.refit_fixed, d.n_insts,
-                           d.refit_lbox + 2 * (size_t)R.leaf_base);
-    for (size_t h = 0; h + 1 < R.off.size(); h++) {
-        const uint32_t n = R.off[h + 1] - R.off[h];
-        if (!n) continue;
-        hipLaunchKernelGGL(refit_node_kernel, blocks((size_t)4 * n), dim3(kRefitWG), 0, stream, d.nodes,
-                           d.refit_blas_order + R.order_at + R.off[h], n, d.refit_lbox);
-    }
-    if (R.n_inst)
-        hipLaunchKernelGGL(refit_instance_box_kernel, blocks(R.n_inst), dim3(kRefitWG), 0, stream, d.refit_fixed,
-                           (const DevInstance*)d.insts, (const float*)d.refit_inst_m, (const QNode*)d.nodes,
-                           (const uint16_t*)d.tables, (const int32_t*)(d.refit_blas_insts + R.inst_at), R.n_inst);
-    return MRT_OK;
-}
-
-// Enqueue on `stream` for mesh m of `kind` (deform_check): the scatters, what the kind needs
-// between them and the world tree (blas: the mesh's BLAS), then the world tree.
-int enqueue_deform(DeviceState& d, int m, int kind, int blas, const float* d_verts, const float* d_verts2, uint32_t nv,
-                   const float* d_normals, uint32_t nn, uint32_t nt, hipStream_t stream) {
-    if (kind == kDeformWorld) return enqueue(d, m, d_verts, nv, d_normals, nn, stream);
+// Enqueue on `stream` for mesh m of `kind` (deform_check; blas: the mesh's BLAS): nv vertices
+// (kDeformMotion: and the time-1 set) and nn normals (d_normals == nullptr: kept) scattered
+// from packed device arrays into the mesh's slices; then, for a mesh of a BLAS, that BLAS's
+// tree and the boxes of its instances, for a motion-blurred mesh the boxes of its nt MBObject
+// lanes; then the world tree.
+int enqueue_mesh(DeviceState& d, int m, int kind, int blas, const float* d_verts, const float* d_verts2, uint32_t nv,
+                 const float* d_normals, uint32_t nn, uint32_t nt, hipStream_t stream) {
+    auto scatter = [&](float4* dst, float4* dst2, const float* src, uint32_t n, float w) {
+        if (n) hipLaunchKernelGGL(refit_scatter_kernel, blocks(n), dim3(kRefitWG), 0, stream, dst, dst2, src, n, w);
+    };
     const bool motion = kind == kDeformMotion && d.has_mb;
-    if (nv)   // a mesh of a BLAS is static: its time-1 copy follows, as in enqueue()
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts + d.vbase[(size_t)m],
-                           kind == kDeformBlas && d.has_mb ? d.verts2 + d.vbase[(size_t)m] : (float4*)nullptr, d_verts, nv, 1.f);
-    if (nv && motion)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nv), dim3(kRefitWG), 0, stream, d.verts2 + d.vbase[(size_t)m],
-                           (float4*)nullptr, d_verts2, nv, 1.f);
-    if (d_normals && nn)
-        hipLaunchKernelGGL(refit_scatter_kernel, blocks(nn), dim3(kRefitWG), 0, stream, d.normals + d.nbase[(size_t)m],
-                           (float4*)nullptr, d_normals, nn, 0.f);
+    const size_t vb = d.vbase[(size_t)m];
+    // a static mesh's time-1 copy follows; a motion-blurred one has its own set
+    scatter(d.verts + vb, d.has_mb && kind != kDeformMotion ? d.verts2 + vb : nullptr, d_verts, nv, 1.f);
+    if (motion) scatter(d.verts2 + vb, nullptr, d_verts2, nv, 1.f);
+    if (d_normals) scatter(d.normals + d.nbase[(size_t)m], nullptr, d_normals, nn, 0.f);
     if (kind == kDeformBlas) {
-        if (const int rc = enqueue_blas(d, blas, stream)) return rc;
+        const DeviceState::BlasRange& R = d.blas[(size_t)blas];
+        enqueue_tree(d, R.tree, stream);
+        if (R.n_inst)
+            hipLaunchKernelGGL(refit_instance_box_kernel, blocks(R.n_inst), dim3(kRefitWG), 0, stream, d.refit_fixed,
+                               (const DevInstance*)d.insts, (const float*)d.refit_inst_m, (const QNode*)d.nodes,
+                               (const uint16_t*)d.tables, (const int32_t*)(d.refit_blas_insts + R.inst_at), R.n_inst);
     } else if (motion && nt && d.mesh_prim0[(size_t)m] >= 0) {
         hipLaunchKernelGGL(refit_motion_box_kernel, blocks(nt), dim3(kRefitWG), 0, stream, d.refit_fixed, d.n_insts,
                            (const int32_t*)d.refit_mbslot, (const uint8_t*)d.pflags, (const PrimShade*)d.prims,
                            (const float4*)d.verts, (const float4*)d.verts2, (uint32_t)d.mesh_prim0[(size_t)m], nt);
     }
-    return enqueue_tree(d, stream);
+    return enqueue_world(d, stream);
 }
 
 // the synchronous entries' staging buffer on replica d holds `need` floats
@@ -486,12 +465,32 @@ int stage_reserve(DeviceState& d, size_t need) {
     return MRT_OK;
 }
 
+// id joins a stale list (Scene::host_mesh_stale, host_blas_stale) once
+void mark_stale(std::vector<int32_t>& list, int32_t id) {
+    if (std::find(list.begin(), list.end(), id) == list.end()) list.push_back(id);
+}
+
 // after a device deform of a mesh of BLAS b: its host nodes and leaves, and the boxes of its
 // instances, are behind the replica's
 void mark_blas_stale(Scene& S, int32_t b) {
-    if (std::find(S.host_blas_stale.begin(), S.host_blas_stale.end(), b) == S.host_blas_stale.end())
-        S.host_blas_stale.push_back(b);
+    mark_stale(S.host_blas_stale, b);
     S.host_inst_stale = true;
+}
+
+// Tree T's host copy from replica d: the boxes of nodes N (perm: canonical -> device numbers;
+// empty: the same) and the triangles of packets L (DLeaf AoS to the canonical SoA).
+int read_tree(const DeviceState& d, const RefitTree& T, const std::vector<int32_t>& perm, std::vector<QNode>& N,
+              std::vector<QLeaf>& L) {
+    std::vector<QNode> DN(T.n_nodes);
+    std::vector<DLeaf> DL(T.n_leaves);
+    if (!DN.empty()) HIP_OK(hipMemcpy(DN.data(), d.nodes + T.node_base, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
+    if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d.leaves + T.leaf_base, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N.size() && i < DN.size(); i++)
+        memcpy(N[i].box, DN[perm.empty() ? i : (size_t)perm[i]].box, sizeof N[i].box);
+    for (size_t i = 0; i < L.size() && i < DL.size(); i++)
+        for (int k = 0; k < 4; k++)
+            for (int c = 0; c < 9; c++) L[i].t[4 * c + k] = DL[i].tri[k][c];
+    return MRT_OK;
 }
 
 }  // namespace
@@ -508,28 +507,21 @@ int sync_host(Scene& s, bool meshes_only) {
     (void)hipGetDevice(&cur);
     HIP_OK(hipSetDevice(d->device));
     HIP_OK(hipDeviceSynchronize());
-    if (s.host_bvh_stale && !meshes_only) {
-        std::vector<QNode> DN(d->n_world_nodes);
-        std::vector<DLeaf> DL(d->n_world_leaves);
-        HIP_OK(hipMemcpy(DN.data(), d->nodes, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
-        if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d->leaves, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < s.nodes.size() && i < DN.size(); i++)
-            memcpy(s.nodes[i].box, DN[d->node_perm.empty() ? i : (size_t)d->node_perm[i]].box, sizeof s.nodes[i].box);
-        for (size_t i = 0; i < s.leaves.size() && i < DL.size(); i++)
-            for (int k = 0; k < 4; k++)
-                for (int c = 0; c < 9; c++) s.leaves[i].t[4 * c + k] = DL[i].tri[k][c];
-    }
+    int rc;
+    if (s.host_bvh_stale && !meshes_only && (rc = read_tree(*d, d->world, d->node_perm, s.nodes, s.leaves))) return rc;
+    std::vector<float4> buf;
+    auto read3 = [&](std::vector<v3>& dst, const float4* src) -> int {
+        buf.resize(dst.size());
+        if (!dst.empty()) HIP_OK(hipMemcpy(buf.data(), src, dst.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < dst.size(); i++) dst[i] = mk(buf[i].x, buf[i].y, buf[i].z);
+        return MRT_OK;
+    };
     for (int32_t m : s.host_mesh_stale) {
         Mesh& M = s.meshes[(size_t)m];
-        std::vector<float4> buf(std::max(M.verts.size(), M.normals.size()));
-        if (!M.verts.empty()) HIP_OK(hipMemcpy(buf.data(), d->verts + d->vbase[(size_t)m], M.verts.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < M.verts.size(); i++) M.verts[i] = mk(buf[i].x, buf[i].y, buf[i].z);
-        if (!M.normals.empty()) HIP_OK(hipMemcpy(buf.data(), d->normals + d->nbase[(size_t)m], M.normals.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < M.normals.size(); i++) M.normals[i] = mk(buf[i].x, buf[i].y, buf[i].z);
-        if (!M.verts2.empty() && M.verts2.size() == M.verts.size() && d->verts2 && s.mesh_blas[(size_t)m] < 0) {   // an async deform's time-1 set
-            HIP_OK(hipMemcpy(buf.data(), d->verts2 + d->vbase[(size_t)m], M.verts2.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < M.verts2.size(); i++) M.verts2[i] = mk(buf[i].x, buf[i].y, buf[i].z);
-        }
+        if ((rc = read3(M.verts, d->verts + d->vbase[(size_t)m]))) return rc;
+        if ((rc = read3(M.normals, d->normals + d->nbase[(size_t)m]))) return rc;
+        if (!M.verts2.empty() && M.verts2.size() == M.verts.size() && d->verts2 && s.mesh_blas[(size_t)m] < 0)   // an async deform's time-1 set
+            if ((rc = read3(M.verts2, d->verts2 + d->vbase[(size_t)m]))) return rc;
     }
     s.host_mesh_stale.clear();
     if (s.host_inst_stale && d->refit_ready && d->n_insts == (int)s.instances.size()) {
@@ -556,16 +548,8 @@ int sync_host(Scene& s, bool meshes_only) {
     if (!meshes_only) {   // the BLASes a deform refitted: boxes and triangles (BLAS nodes keep their order on the device)
         for (int32_t b : s.host_blas_stale) {
             if ((size_t)b >= d->blas.size() || (size_t)b >= s.blas.size()) continue;
-            const DeviceState::BlasRange& R = d->blas[(size_t)b];
             Blas& B = s.blas[(size_t)b];
-            std::vector<QNode> DN(R.n_nodes);
-            std::vector<DLeaf> DL(R.n_leaves);
-            if (!DN.empty()) HIP_OK(hipMemcpy(DN.data(), d->nodes + R.node_base, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
-            if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d->leaves + R.leaf_base, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < B.nodes.size() && i < DN.size(); i++) memcpy(B.nodes[i].box, DN[i].box, sizeof B.nodes[i].box);
-            for (size_t i = 0; i < B.leaves.size() && i < DL.size(); i++)
-                for (int k = 0; k < 4; k++)
-                    for (int c = 0; c < 9; c++) B.leaves[i].t[4 * c + k] = DL[i].tri[k][c];
+            if ((rc = read_tree(*d, d->blas[(size_t)b].tree, {}, B.nodes, B.leaves))) return rc;
         }
         s.host_blas_stale.clear();
     }
@@ -577,6 +561,34 @@ int sync_host(Scene& s, bool meshes_only) {
 }
 
 namespace {
+
+// The device half of a synchronous entry, replica by replica: wait for the device (no frame
+// in flight may read the arrays while they change), prepare, fill(d) copies the entry's
+// arrays into a stage of stage_floats floats, enqueue(d) runs between the replica's event
+// pair (refit_ms: the current replica's), and the binning box follows the refitted root.
+template <typename Fill, typename Enqueue>
+int refit_replicas(Scene& S, size_t stage_floats, float* refit_ms, Fill fill, Enqueue enqueue) {
+    int rc;
+    DeviceState* cur = S.dev ? S.dev : S.devs[0];
+    for (DeviceState* d : S.devs) {
+        HIP_OK(hipSetDevice(d->device));
+        HIP_OK(hipDeviceSynchronize());
+        if ((rc = prepare(S, *d))) return rc;
+        if ((rc = stage_reserve(*d, stage_floats))) return rc;
+        if ((rc = fill(*d))) return rc;
+        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
+        if ((rc = enqueue(*d))) return rc;
+        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
+        HIP_OK(hipEventSynchronize(d->refit_ev1));
+        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
+        QNode root;
+        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
+        root_box(root, d->bb_lo, d->bb_hi);
+    }
+    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
+    HIP_OK(hipSetDevice(cur->device));
+    return MRT_OK;
+}
 
 // The synchronous entries after their argument checks: mesh `mesh` of `kind` (deform_check;
 // mrt_scene_update_mesh: kDeformWorld) takes verts (verts2: kDeformMotion) and normals.
@@ -600,36 +612,60 @@ int update_sync(Scene& S, int mesh, int kind, const float* verts, const float* v
     set_host();
     const uint32_t nv = (uint32_t)M.verts.size(), nn = normals ? (uint32_t)M.normals.size() : 0u;
     const uint32_t nv2 = kind == kDeformMotion ? nv : 0u;
-    DeviceState* cur = S.dev ? S.dev : S.devs[0];
-    for (DeviceState* d : S.devs) {
-        HIP_OK(hipSetDevice(d->device));
-        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
-        if ((rc = prepare(S, *d))) return rc;
-        if ((rc = stage_reserve(*d, ((size_t)nv + nn + nv2) * 3))) return rc;
-        if (nv) HIP_OK(hipMemcpy(d->refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (nn) HIP_OK(hipMemcpy(d->refit_stage + (size_t)nv * 3, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (nv2) HIP_OK(hipMemcpy(d->refit_stage + ((size_t)nv + nn) * 3, verts2, (size_t)nv2 * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (!M.tidx.empty() && d->tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
+    const size_t at_n = (size_t)nv * 3, at_v2 = ((size_t)nv + nn) * 3;   // the stage: vertices, normals, time-1 vertices
+    auto fill = [&](DeviceState& d) -> int {
+        if (nv) HIP_OK(hipMemcpy(d.refit_stage, verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (nn) HIP_OK(hipMemcpy(d.refit_stage + at_n, normals, (size_t)nn * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (nv2) HIP_OK(hipMemcpy(d.refit_stage + at_v2, verts2, (size_t)nv2 * 3 * sizeof(float), hipMemcpyHostToDevice));
+        if (!M.tidx.empty() && d.tans && !M.tan.empty()) {   // the tangent frames of the new vertices (mesh_tangents)
             std::vector<float4> T(M.tan.size()), B(M.btan.size());
             for (size_t i = 0; i < T.size(); i++) T[i] = make_float4(M.tan[i].x, M.tan[i].y, M.tan[i].z, 0.f);
             for (size_t i = 0; i < B.size(); i++) B[i] = make_float4(M.btan[i].x, M.btan[i].y, M.btan[i].z, 0.f);
-            HIP_OK(hipMemcpy(d->tans + d->nbase[(size_t)mesh], T.data(), T.size() * sizeof(float4), hipMemcpyHostToDevice));
-            HIP_OK(hipMemcpy(d->btans + d->nbase[(size_t)mesh], B.data(), B.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d.tans + d.nbase[(size_t)mesh], T.data(), T.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d.btans + d.nbase[(size_t)mesh], B.data(), B.size() * sizeof(float4), hipMemcpyHostToDevice));
         }
-        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
-        if ((rc = enqueue_deform(*d, mesh, kind, blas, d->refit_stage, d->refit_stage + ((size_t)nv + nn) * 3, nv,
-                                 nn ? d->refit_stage + (size_t)nv * 3 : nullptr, nn, (uint32_t)M.nt(), nullptr)))
-            return rc;
-        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
-        HIP_OK(hipEventSynchronize(d->refit_ev1));
-        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
-        QNode root;   // the binning box follows the refitted root
-        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
-        root_box(root, d->bb_lo, d->bb_hi);
-    }
-    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
+        return MRT_OK;
+    };
+    auto enqueue = [&](DeviceState& d) -> int {
+        return enqueue_mesh(d, mesh, kind, blas, d.refit_stage, d.refit_stage + at_v2, nv, nn ? d.refit_stage + at_n : nullptr, nn,
+                            (uint32_t)M.nt(), nullptr);
+    };
+    if ((rc = refit_replicas(S, at_v2 + (size_t)nv2 * 3, refit_ms, fill, enqueue))) return rc;
     if (kind == kDeformBlas) mark_blas_stale(S, blas);
-    HIP_OK(hipSetDevice(cur->device));
+    return MRT_OK;
+}
+
+// What an async entry (`name`: "update_mesh", ...) needs beyond its argument checks: no
+// tangent frames to recompute (M: the mesh it moves, or nullptr) and the scene on exactly
+// one device, which becomes the current one and is prepared.
+int async_ready(Scene& S, const Mesh* M, const std::string& name) {
+    if (M && !M->tidx.empty()) {
+        set_error(name + "_async: the mesh has texture coordinates (its tangent frames are recomputed on the host: use mrt_scene_" +
+                  name + ")");
+        return MRT_ERR_INVALID;
+    }
+    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
+        set_error(name + "_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
+        return MRT_ERR_INVALID;
+    }
+    HIP_OK(hipSetDevice(S.dev->device));
+    return prepare(S, *S.dev);
+}
+
+// The async mesh entries after their argument checks: enqueue and mark the host copy stale.
+int mesh_async(Scene& S, int mesh, int kind, const std::string& name, const float* d_verts, const float* d_verts2,
+               const float* d_normals, hipStream_t stream) {
+    if (!d_verts) { set_error(name + ": null vertices"); return MRT_ERR_INVALID; }
+    const Mesh& M = S.meshes[(size_t)mesh];
+    int rc;
+    if ((rc = async_ready(S, &M, name))) return rc;
+    const int32_t blas = S.mesh_blas[(size_t)mesh];
+    if ((rc = enqueue_mesh(*S.dev, mesh, kind, blas, d_verts, d_verts2, (uint32_t)M.verts.size(), d_normals,
+                           (uint32_t)M.normals.size(), (uint32_t)M.nt(), stream)))
+        return rc;
+    S.host_bvh_stale = true;
+    if (kind == kDeformBlas) mark_blas_stale(S, blas);
+    mark_stale(S.host_mesh_stale, mesh);
     return MRT_OK;
 }
 
@@ -670,54 +706,15 @@ int mrt_scene_deform_mesh_async(mrt_scene* s, int mesh, const float* d_verts, co
     int rc = deform_check(S, mesh, nullptr, nullptr, d_verts2 != nullptr, nullptr, &kind);   // ids and kinds: the arrays are on the device
     if (rc) return rc;
     if (kind == kDeformWorld) return mrt_scene_update_mesh_async(s, mesh, d_verts, d_normals, stream);
-    if (!d_verts) { set_error("deform_mesh: null vertices"); return MRT_ERR_INVALID; }
-    Mesh& M = S.meshes[(size_t)mesh];
-    if (!M.tidx.empty()) {
-        set_error("deform_mesh_async: the mesh has texture coordinates (its tangent frames are recomputed on the host: use mrt_scene_deform_mesh)");
-        return MRT_ERR_INVALID;
-    }
-    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
-        set_error("deform_mesh_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
-        return MRT_ERR_INVALID;
-    }
-    DeviceState& d = *S.dev;
-    HIP_OK(hipSetDevice(d.device));
-    if ((rc = prepare(S, d))) return rc;
-    const int32_t blas = S.mesh_blas[(size_t)mesh];
-    if ((rc = enqueue_deform(d, mesh, kind, blas, d_verts, d_verts2, (uint32_t)M.verts.size(), d_normals,
-                             (uint32_t)M.normals.size(), (uint32_t)M.nt(), (hipStream_t)stream)))
-        return rc;
-    S.host_bvh_stale = true;
-    if (kind == kDeformBlas) mark_blas_stale(S, blas);
-    if (std::find(S.host_mesh_stale.begin(), S.host_mesh_stale.end(), mesh) == S.host_mesh_stale.end())
-        S.host_mesh_stale.push_back(mesh);
-    return MRT_OK;
+    return mesh_async(S, mesh, kind, "deform_mesh", d_verts, d_verts2, d_normals, (hipStream_t)stream);
 }
 
 int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_normals, void* stream) {
     if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
     Scene& S = s->impl;
-    int rc = refit_check(S, mesh, nullptr, nullptr);
+    const int rc = refit_check(S, mesh, nullptr, nullptr);
     if (rc) return rc;
-    if (!d_verts) { set_error("update_mesh: null vertices"); return MRT_ERR_INVALID; }
-    Mesh& M = S.meshes[(size_t)mesh];
-    if (!M.tidx.empty()) {
-        set_error("update_mesh_async: the mesh has texture coordinates (its tangent frames are recomputed on the host: use mrt_scene_update_mesh)");
-        return MRT_ERR_INVALID;
-    }
-    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
-        set_error("update_mesh_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
-        return MRT_ERR_INVALID;
-    }
-    DeviceState& d = *S.dev;
-    HIP_OK(hipSetDevice(d.device));
-    if ((rc = prepare(S, d))) return rc;
-    if ((rc = enqueue(d, mesh, d_verts, (uint32_t)M.verts.size(), d_normals, (uint32_t)M.normals.size(), (hipStream_t)stream)))
-        return rc;
-    S.host_bvh_stale = true;
-    if (std::find(S.host_mesh_stale.begin(), S.host_mesh_stale.end(), mesh) == S.host_mesh_stale.end())
-        S.host_mesh_stale.push_back(mesh);
-    return MRT_OK;
+    return mesh_async(S, mesh, kDeformWorld, "update_mesh", d_verts, nullptr, d_normals, (hipStream_t)stream);
 }
 
 int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n, const float* m16s, float* refit_ms) {
@@ -742,27 +739,15 @@ int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n, cons
         return MRT_OK;
     }
     if ((rc = sync_host(S, true))) return rc;   // the host instances are current from here (the hierarchy stays on the device)
-    DeviceState* cur = S.dev ? S.dev : S.devs[0];
-    for (DeviceState* d : S.devs) {
-        HIP_OK(hipSetDevice(d->device));
-        HIP_OK(hipDeviceSynchronize());   // no frame in flight may read the arrays while they change
-        if ((rc = prepare(S, *d))) return rc;
-        if ((rc = stage_reserve(*d, (size_t)n * 17))) return rc;   // n matrices, then n ids
-        int32_t* d_ids = ids ? (int32_t*)(d->refit_stage + (size_t)n * 16) : nullptr;
-        HIP_OK(hipMemcpy(d->refit_stage, m16s, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice));
-        if (ids) HIP_OK(hipMemcpy(d_ids, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_OK(hipEventRecord(d->refit_ev0, nullptr));
-        if ((rc = enqueue_instances(*d, d->refit_stage, d_ids, 0, (uint32_t)n, nullptr))) return rc;
-        HIP_OK(hipEventRecord(d->refit_ev1, nullptr));
-        HIP_OK(hipEventSynchronize(d->refit_ev1));
-        if (d == cur && refit_ms) HIP_OK(hipEventElapsedTime(refit_ms, d->refit_ev0, d->refit_ev1));
-        QNode root;   // the binning box follows the refitted root
-        HIP_OK(hipMemcpy(&root, d->nodes, sizeof root, hipMemcpyDeviceToHost));
-        root_box(root, d->bb_lo, d->bb_hi);
-    }
+    auto d_ids = [&](DeviceState& d) { return ids ? (int32_t*)(d.refit_stage + (size_t)n * 16) : nullptr; };   // after the matrices
+    auto fill = [&](DeviceState& d) -> int {
+        HIP_OK(hipMemcpy(d.refit_stage, m16s, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice));
+        if (ids) HIP_OK(hipMemcpy(d_ids(d), ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        return MRT_OK;
+    };
+    auto enqueue = [&](DeviceState& d) -> int { return enqueue_instances(d, d.refit_stage, d_ids(d), 0, (uint32_t)n, nullptr); };
+    if ((rc = refit_replicas(S, (size_t)n * 17, refit_ms, fill, enqueue))) return rc;   // n matrices, then n ids
     apply();
-    S.host_bvh_stale = true;   // mrt_scene_bvh_export reads the device's arrays back
-    HIP_OK(hipSetDevice(cur->device));
     return MRT_OK;
 }
 
@@ -773,14 +758,8 @@ int mrt_scene_update_instances_async(mrt_scene* s, int32_t first, int32_t n, con
     int rc = instances_check(S, nullptr, first, n, nullptr, nullptr);   // the range: the kernel trusts its ids
     if (rc) return rc;
     if (n == 0) return MRT_OK;
-    if (S.dev_dirty || S.devs.size() != 1 || !S.dev) {
-        set_error("update_instances_async needs the scene uploaded to exactly one device (mrt_scene_upload)");
-        return MRT_ERR_INVALID;
-    }
-    DeviceState& d = *S.dev;
-    HIP_OK(hipSetDevice(d.device));
-    if ((rc = prepare(S, d))) return rc;
-    if ((rc = enqueue_instances(d, d_m16s, nullptr, first, (uint32_t)n, (hipStream_t)stream))) return rc;
+    if ((rc = async_ready(S, nullptr, "update_instances"))) return rc;
+    if ((rc = enqueue_instances(*S.dev, d_m16s, nullptr, first, (uint32_t)n, (hipStream_t)stream))) return rc;
     S.host_bvh_stale = true;
     S.host_inst_stale = true;
     return MRT_OK;

@@ -279,11 +279,11 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
     std::vector<int32_t> blas_root(s.blas.size());
     d.blas.assign(s.blas.size(), DeviceState::BlasRange());
     for (size_t b = 0; b < s.blas.size(); b++) {
-        d.blas[b].leaf_base = (uint32_t)DL.size();
+        d.blas[b].tree.leaf_base = (uint32_t)DL.size();
         blas_root[b] = append(s.blas[b].nodes, s.blas[b].leaves, nullptr, &s.blas[b]);
-        d.blas[b].n_nodes = (uint32_t)s.blas[b].nodes.size();
-        d.blas[b].n_leaves = (uint32_t)s.blas[b].leaves.size();
-        d.blas[b].shade_base = shade_base[b];
+        d.blas[b].tree.n_nodes = (uint32_t)s.blas[b].nodes.size();
+        d.blas[b].tree.n_leaves = (uint32_t)s.blas[b].leaves.size();
+        d.blas[b].tree.shade_base = shade_base[b];
     }
     d.n_leaves_all = (uint32_t)DL.size();
     // The world hierarchy's first kLdsNodes nodes in breadth-first order get device
@@ -320,9 +320,10 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
         for (int32_t& br : blas_root) br = perm[(size_t)br];
         d.node_perm.assign(perm.begin(), perm.begin() + (ptrdiff_t)nw);
     }
-    for (size_t b = 0; b < s.blas.size(); b++) d.blas[b].node_base = (uint32_t)blas_root[b];   // BLAS nodes keep their numbers
-    d.n_world_nodes = (uint32_t)nw;
-    d.n_world_leaves = (uint32_t)s.leaves.size();
+    for (size_t b = 0; b < s.blas.size(); b++) d.blas[b].tree.node_base = (uint32_t)blas_root[b];   // BLAS nodes keep their numbers
+    d.world.n_nodes = (uint32_t)nw;
+    d.world.n_leaves = (uint32_t)s.leaves.size();
+    d.world.fixed_lanes = true;
     d.vbase = vbase;
     d.nbase = nbase;
     for (QNode& q : DN) q.pad[0] = slot_kinds(q.child);   // the walks read the slot kinds (node_kinds)
