@@ -1060,6 +1060,26 @@ static int launch_chain_adaptive(Scene& s, StreamCtx& c, RenderParams& P, bool c
     return MRT_OK;
 }
 
+// The bracket of a query that is not a render (trace_async, hit_surfaces_async): the stream's
+// context with `ctr_bytes` of its counters cleared and ev0 recorded; then the caller's launch;
+// then end_launch.
+static int begin_query(Scene& s, DeviceState& d, hipStream_t stream, size_t ctr_bytes, bool supplied, StreamCtx*& c) {
+    if (const int rc = get_ctx(d, stream, c)) return rc;
+    s.stats_final = false;
+    HIP_OK(hipMemsetAsync(c->ctr, 0, ctr_bytes, stream));
+    c->last_was_render = false;
+    c->supplied = supplied;
+    HIP_OK(hipEventRecord(c->ev0, stream));
+    return MRT_OK;
+}
+// after the last launch of a render or a query: its launch error, ev1, and c is what the statistics read
+static int end_launch(DeviceState& d, StreamCtx& c, hipStream_t stream) {
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c.ev1, stream));
+    d.last = &c;
+    return MRT_OK;
+}
+
 // Two launches on `stream`: primary rays -> hit records, then shading with
 // shadow rays.  Events bracket both (kernel_ms covers the whole frame).  With
 // adaptive supersampling (subdivs > 1) one fused launch (kernel 3) instead.
@@ -1118,9 +1138,7 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
     // every path ends here, after its last launch (and its evm record)
     auto done = [&]() -> int {
         c.last_was_render = true;
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipEventRecord(c.ev1, stream));
-        d.last = &c;
+        if (const int r = end_launch(d, c, stream)) return r;
         s.last = mrt_stats{};
         return MRT_OK;
     };
@@ -1252,6 +1270,85 @@ static int launch_render(Scene& s, RenderParams& P, size_t slots, bool count, hi
 using namespace mrt;
 
 // ================================================================== C ABI (device side; the rest: host_api.cpp)
+// What the entries share:
+//   current_replica   the scene's current replica (device 0 before the first upload), made current
+//   ray_args_check    the argument checks of the caller-ray entries, before any device call
+//   Staged            the device copies of a synchronous entry's host arrays, freed when it returns
+//   begin_query / end_launch (above launch_render)   the bracket of a launch that is not a render
+//   frame_params, seed_or_default, ensure_frame      one-camera frame setup
+// A synchronous entry is: checks, current_replica, stage in, its async body, copy out, its own
+// closing status.
+static int current_replica(Scene& S, DeviceState*& d) {
+    const int dev = S.dev ? S.dev->device : 0;
+    if (const int rc = ensure_device(S, dev)) return rc;
+    HIP_OK(hipSetDevice(dev));
+    d = S.dev;
+    return MRT_OK;
+}
+
+static constexpr size_t kMaxRayBatch = size_t(1) << 28;
+static bool any_null(std::initializer_list<const void*> a) { return std::find(a.begin(), a.end(), nullptr) != a.end(); }
+// `need`: the arrays an entry requires when n > 0, `what` names them ("null <what> array");
+// row_width: 0 from an entry that has none
+static int ray_args_check(const mrt_scene* s, size_t n, int32_t row_width, std::initializer_list<const void*> need,
+                          const char* what) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (n && any_null(need)) { set_error(std::string("null ") + what + " array"); return MRT_ERR_INVALID; }
+    if (row_width < 0) { set_error("row_width must be >= 0"); return MRT_ERR_INVALID; }
+    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    return MRT_OK;
+}
+
+// One allocation per array per call; after a failure (rc) every further call does nothing.
+struct Staged {
+    std::vector<void*> bufs;
+    int rc = MRT_OK;
+    ~Staged() { for (void* p : bufs) (void)hipFree(p); }
+    template <typename T> T* out(size_t bytes) {
+        void* p = nullptr;
+        if (rc == MRT_OK && (rc = alloc(p, bytes)) == MRT_OK) bufs.push_back(p);
+        return static_cast<T*>(p);
+    }
+    template <typename T> T* in(const T* host, size_t bytes) {   // a null host array stays null
+        T* p = host ? out<T>(bytes) : nullptr;
+        if (p) rc = copy(p, host, bytes, hipMemcpyHostToDevice);
+        return p;
+    }
+    int back(void* host, const void* dev, size_t bytes) { return copy(host, dev, bytes, hipMemcpyDeviceToHost); }
+private:
+    static int alloc(void*& p, size_t bytes) { HIP_OK(hipMalloc(&p, bytes)); return MRT_OK; }
+    static int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        HIP_OK(hipMemcpy(dst, src, bytes, kind)); return MRT_OK;
+    }
+};
+
+static uint32_t seed_or_default(uint32_t seed) { return seed ? seed : 0x5EEDu; }
+
+// the parameters of a one-camera frame: tiles of 8x8 pixels
+static int frame_params(const Scene& S, const mrt_camera* cam, const mrt_render_opts* opts, RenderParams& P) {
+    fill_params(S, P);
+    if (const int rc = host_camera(cam, opts->width, opts->height, P.cam[0])) return rc;
+    P.seed = seed_or_default(opts->seed);
+    P.mode = 0;
+    P.tiles_x = (opts->width + 7) / 8;
+    P.n_tiles = P.tiles_x * ((opts->height + 7) / 8);
+    return MRT_OK;
+}
+
+// the replica's frame buffers of the synchronous renders hold px pixels; sync_stream: what may still read the old ones
+static int ensure_frame(DeviceState& d, size_t px, const hipStream_t* sync_stream) {
+    if (px <= d.frame_px) return MRT_OK;
+    if (sync_stream) HIP_OK(hipStreamSynchronize(*sync_stream));
+    if (d.d_rgb) (void)hipFree(d.d_rgb);
+    if (d.d_rgb8) (void)hipFree(d.d_rgb8);
+    d.d_rgb = nullptr; d.d_rgb8 = nullptr; d.frame_px = 0;
+    HIP_OK(hipMalloc((void**)&d.d_rgb, px * 12));
+    HIP_OK(hipMalloc((void**)&d.d_rgb8, px * 3));
+    d.frame_px = px;
+    return MRT_OK;
+}
+
 extern "C" {
 
 int mrt_device_count(void) {
@@ -1279,12 +1376,7 @@ int mrt_render_frame_async(mrt_scene* s, const mrt_camera* cam, const mrt_render
     if (rc) return rc;
     HIP_OK(hipSetDevice(opts->device));
     RenderParams P{};
-    fill_params(S, P);
-    if ((rc = host_camera(cam, opts->width, opts->height, P.cam[0]))) return rc;
-    P.seed = opts->seed ? opts->seed : 0x5EEDu;
-    P.mode = 0;
-    P.tiles_x = (opts->width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((opts->height + 7) / 8);
+    if ((rc = frame_params(S, cam, opts, P))) return rc;
     P.out_rgb = d_rgb;
     P.out_rgb8 = d_rgb8;
     rc = launch_render(S, P, (size_t)opts->width * opts->height, opts->count_visits != 0, (hipStream_t)stream,
@@ -1308,7 +1400,7 @@ static int render_batch(mrt_scene* s, const mrt_camera* cams, int32_t n_cams, co
     fill_params(S, P);
     for (int f = 0; f < n_cams; f++)
         if ((rc = host_camera(cams + f, opts->width, opts->height, P.cam[f]))) return rc;
-    P.seed = opts->seed ? opts->seed : 0x5EEDu;
+    P.seed = seed_or_default(opts->seed);
     P.mode = 1;
     P.frame_out = frame_out ? 1 : 0;
     P.buckets = d_items;
@@ -1464,16 +1556,8 @@ static int render_shared(mrt_scene* s, const mrt_camera* cam, const mrt_render_o
     if (!dc.gather_stream) HIP_OK(hipStreamCreateWithFlags(&dc.gather_stream, hipStreamNonBlocking));
     const hipStream_t gs = dc.gather_stream;
     const size_t px = (size_t)W * H;
-    if (px > dc.frame_px) {
-        HIP_OK(hipStreamSynchronize(gs));
-        if (dc.d_rgb) (void)hipFree(dc.d_rgb);
-        if (dc.d_rgb8) (void)hipFree(dc.d_rgb8);
-        dc.d_rgb = nullptr; dc.d_rgb8 = nullptr; dc.frame_px = 0;
-        HIP_OK(hipMalloc((void**)&dc.d_rgb, px * 12));
-        HIP_OK(hipMalloc((void**)&dc.d_rgb8, px * 3));
-        dc.frame_px = px;
-    }
-    if ((rc = ensure_buf(reinterpret_cast<void*&>(dc.g_tiles), dc.g_tiles_cap, (size_t)bpf * tile_f * sizeof(float), gs)) ||
+    if ((rc = ensure_frame(dc, px, &gs)) ||
+        (rc = ensure_buf(reinterpret_cast<void*&>(dc.g_tiles), dc.g_tiles_cap, (size_t)bpf * tile_f * sizeof(float), gs)) ||
         (rc = ensure_buf(reinterpret_cast<void*&>(dc.g_items), dc.g_items_cap, (size_t)bpf * sizeof(int32_t), gs)))
         return rc;
     struct Share {
@@ -1628,21 +1712,9 @@ int mrt_render(mrt_scene* s, const mrt_camera* cam, const mrt_render_opts* opts,
     HIP_OK(hipSetDevice(opts->device));
     DeviceState& d = *S.dev;
     size_t px = (size_t)opts->width * opts->height;
-    if (px > d.frame_px) {
-        if (d.d_rgb) (void)hipFree(d.d_rgb);
-        if (d.d_rgb8) (void)hipFree(d.d_rgb8);
-        d.d_rgb = nullptr; d.d_rgb8 = nullptr; d.frame_px = 0;
-        HIP_OK(hipMalloc((void**)&d.d_rgb, px * 12));
-        HIP_OK(hipMalloc((void**)&d.d_rgb8, px * 3));
-        d.frame_px = px;
-    }
+    if ((rc = ensure_frame(d, px, nullptr))) return rc;
     RenderParams P{};
-    fill_params(S, P);
-    if ((rc = host_camera(cam, opts->width, opts->height, P.cam[0]))) return rc;
-    P.seed = opts->seed ? opts->seed : 0x5EEDu;
-    P.mode = 0;
-    P.tiles_x = (opts->width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((opts->height + 7) / 8);
+    if ((rc = frame_params(S, cam, opts, P))) return rc;
     P.out_rgb = d.d_rgb;
     P.out_rgb8 = d.d_rgb8;
     if ((rc = launch_render(S, P, px, opts->count_visits != 0, nullptr, hits != nullptr || opts->want_hits))) return rc;
@@ -1659,19 +1731,8 @@ int mrt_render(mrt_scene* s, const mrt_camera* cam, const mrt_render_opts* opts,
     return MRT_OK;
 }
 
-// ---- Scene::sampleScene for caller rays (ray mode of the render dispatch, P.mode == 2)
-static constexpr size_t kMaxRayBatch = size_t(1) << 28;
-// the argument checks of both entries: before any device call
-static int sample_rays_check(const mrt_scene* s, const float* o, const float* d, size_t n, int32_t row_width,
-                             const float* rgb) {
-    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
-    if (n && (!o || !d || !rgb)) { set_error("null ray / output array"); return MRT_ERR_INVALID; }
-    if (row_width < 0) { set_error("row_width must be >= 0"); return MRT_ERR_INVALID; }
-    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
-    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
-    return MRT_OK;
-}
-
+// ---- Scene::sampleScene for caller rays (ray mode of the render dispatch, P.mode == 2), and its
+// hit / miss branch for caller (ray, hit) pairs (mrt_shade_hits)
 // the ray mode of the render dispatch on device arrays (checked by the caller, n > 0);
 // d_supplied: the caller's hit records in the primary launch's place (mrt_shade_hits)
 static int ray_batch_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
@@ -1679,13 +1740,12 @@ static int ray_batch_async(mrt_scene* s, const float* d_o, const float* d_d, con
                            const mrt_hit* d_supplied, void* stream) {
     int rc;
     Scene& S = s->impl;
-    const int dev = S.dev ? S.dev->device : 0;
-    if ((rc = ensure_device(S, dev))) return rc;
-    HIP_OK(hipSetDevice(dev));
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(S, dp))) return rc;
     RenderParams P{};
     fill_params(S, P);
     P.min_subdivs = P.max_subdivs = 1;   // one sampleScene per ray
-    P.seed = seed ? seed : 0x5EEDu;
+    P.seed = seed_or_default(seed);
     P.mode = 2;
     P.rays_o = d_o;
     P.rays_d = d_d;
@@ -1700,7 +1760,7 @@ static int ray_batch_async(mrt_scene* s, const float* d_o, const float* d_d, con
     if ((rc = launch_render(S, P, n, count_visits != 0, (hipStream_t)stream, d_hits != nullptr, d_supplied))) return rc;
     S.last.primary_rays = (uint64_t)n;
     if (d_hits) {
-        const DeviceState& d = *S.dev;
+        const DeviceState& d = *dp;
         const int g = (int)std::min<size_t>((n + 255) / 256, (size_t)d.cus * 8);
         hipLaunchKernelGGL(hit_records_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, d.last->hitbuf, n, d.insts,
                            (int32_t)d.n_insts, (int32_t)d.n_world, d_hits);
@@ -1709,24 +1769,41 @@ static int ray_batch_async(mrt_scene* s, const float* d_o, const float* d_d, con
     return MRT_OK;
 }
 
+// the same on host arrays (checked by the caller, n > 0): hits out (nullable), or supplied in
+static int ray_batch_sync(mrt_scene* s, const float* o, const float* d, const float* time, size_t n, int32_t row_width,
+                          uint32_t seed, int32_t count_visits, float* rgb, mrt_hit* hits, const mrt_hit* supplied) {
+    int rc;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(s->impl, dp))) return rc;
+    Staged st;
+    const float *bo = st.in(o, n * 12), *bd = st.in(d, n * 12);
+    const mrt_hit* bs = st.in(supplied, n * sizeof(mrt_hit));
+    const float* bt = st.in(time, n * 4);
+    float* brgb = st.out<float>(n * 12);
+    mrt_hit* bh = hits ? st.out<mrt_hit>(n * sizeof(mrt_hit)) : nullptr;
+    if (st.rc) return st.rc;
+    if ((rc = ray_batch_async(s, bo, bd, bt, n, row_width, seed, count_visits, brgb, bh, bs, nullptr))) return rc;
+    if ((rc = st.back(rgb, brgb, n * 12))) return rc;
+    if (hits && (rc = st.back(hits, bh, n * sizeof(mrt_hit)))) return rc;
+    mrt_stats tmp;
+    return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
+}
+
 int mrt_sample_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, size_t n,
                           int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, mrt_hit* d_hits,
                           void* stream) {
-    const int rc = sample_rays_check(s, d_o, d_d, n, row_width, d_rgb);
+    const int rc = ray_args_check(s, n, row_width, {d_o, d_d, d_rgb}, "ray / output");
     if (rc || n == 0) return rc;
     return ray_batch_async(s, d_o, d_d, d_time, n, row_width, seed, count_visits, d_rgb, d_hits, nullptr, stream);
 }
 
-// ---- the hit / miss branch of Scene::sampleScene for caller (ray, hit) pairs (mrt_shade_hits)
-static int shade_hits_check(const mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n,
-                            int32_t row_width, const float* rgb) {
-    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
-    if (n && (!o || !d || !hits || !rgb)) { set_error("null ray / hit / output array"); return MRT_ERR_INVALID; }
-    if (row_width < 0) { set_error("row_width must be >= 0"); return MRT_ERR_INVALID; }
-    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
-    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
-    return MRT_OK;
+int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* time, size_t n, int32_t row_width,
+                    uint32_t seed, int32_t count_visits, float* rgb, mrt_hit* hits) {
+    const int rc = ray_args_check(s, n, row_width, {o, d, rgb}, "ray / output");
+    if (rc || n == 0) return rc;
+    return ray_batch_sync(s, o, d, time, n, row_width, seed, count_visits, rgb, hits, nullptr);
 }
+
 // the synchronous entries refuse a bad record of the host array, naming the first
 static int host_hits_check(const mrt_scene* s, const mrt_hit* hits, size_t n) {
     const char* why = "";
@@ -1738,53 +1815,20 @@ static int host_hits_check(const mrt_scene* s, const mrt_hit* hits, size_t n) {
 
 int mrt_shade_hits_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const mrt_hit* d_hits,
                          size_t n, int32_t row_width, uint32_t seed, int32_t count_visits, float* d_rgb, void* stream) {
-    const int rc = shade_hits_check(s, d_o, d_d, d_hits, n, row_width, d_rgb);
+    const int rc = ray_args_check(s, n, row_width, {d_o, d_d, d_hits, d_rgb}, "ray / hit / output");
     if (rc || n == 0) return rc;
     return ray_batch_async(s, d_o, d_d, d_time, n, row_width, seed, count_visits, d_rgb, nullptr, d_hits, stream);
 }
 
 int mrt_shade_hits(mrt_scene* s, const float* o, const float* d, const float* time, const mrt_hit* hits, size_t n,
                    int32_t row_width, uint32_t seed, int32_t count_visits, float* rgb) {
-    int rc = shade_hits_check(s, o, d, hits, n, row_width, rgb);
+    int rc = ray_args_check(s, n, row_width, {o, d, hits, rgb}, "ray / hit / output");
     if (rc || n == 0) return rc;
     if ((rc = host_hits_check(s, hits, n))) return rc;
-    Scene& S = s->impl;
-    const int dev = S.dev ? S.dev->device : 0;
-    if ((rc = ensure_device(S, dev))) return rc;
-    HIP_OK(hipSetDevice(dev));
-    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *brgb = nullptr;
-    mrt_hit* bh = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void**)&bo, n * 12));
-        HIP_OK(hipMalloc((void**)&bd, n * 12));
-        HIP_OK(hipMalloc((void**)&brgb, n * 12));
-        HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
-        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
-        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bh, hits, n * sizeof(mrt_hit), hipMemcpyHostToDevice));
-        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
-        int r = ray_batch_async(s, bo, bd, bt, n, row_width, seed, count_visits, brgb, nullptr, bh, nullptr);
-        if (r) return r;
-        HIP_OK(hipMemcpy(rgb, brgb, n * 12, hipMemcpyDeviceToHost));
-        mrt_stats tmp;
-        return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
-    };
-    rc = run();
-    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(brgb); (void)hipFree(bh);
-    return rc;
+    return ray_batch_sync(s, o, d, time, n, row_width, seed, count_visits, rgb, nullptr, hits);
 }
 
 // ---- Ray::getPoint + HitInfo::getAllInfos for caller (ray, hit) pairs (mrt_hit_surfaces)
-static int hit_surfaces_check(const mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n,
-                              const mrt_surface* out) {
-    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
-    if (n && (!o || !d || !hits || !out)) { set_error("null ray / hit / output array"); return MRT_ERR_INVALID; }
-    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
-    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
-    return MRT_OK;
-}
-
 // the replica's SurfaceGroup table, built on first use
 static int surface_groups(const Scene& S, DeviceState& d) {
     std::lock_guard<std::mutex> g(d.mu);
@@ -1818,95 +1862,48 @@ static int surface_groups(const Scene& S, DeviceState& d) {
     return MRT_OK;
 }
 
-int mrt_hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
-                           mrt_surface* d_out, void* stream) {
-    int rc = hit_surfaces_check(s, d_o, d_d, d_hits, n, d_out);
-    if (rc || n == 0) return rc;
+// on device arrays (checked by the caller, n > 0)
+static int hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
+                              mrt_surface* d_out, hipStream_t stream) {
+    int rc;
     Scene& S = s->impl;
-    const int dev = S.dev ? S.dev->device : 0;
-    if ((rc = ensure_device(S, dev))) return rc;
-    HIP_OK(hipSetDevice(dev));
-    DeviceState& d = *S.dev;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(S, dp))) return rc;
+    DeviceState& d = *dp;
     if ((rc = surface_groups(S, d))) return rc;
-    StreamCtx* cp = nullptr;
-    if ((rc = get_ctx(d, (hipStream_t)stream, cp))) return rc;
-    StreamCtx& c = *cp;
-    S.stats_final = false;
-    HIP_OK(hipMemsetAsync(c.ctr, 0, kCtrBytes, (hipStream_t)stream));
-    c.last_was_render = false;
-    c.supplied = true;
+    StreamCtx* c = nullptr;
+    if ((rc = begin_query(S, d, stream, kCtrBytes, true, c))) return rc;
     RenderParams P{};
     fill_params(S, P);
-    P.ctr = c.ctr;
+    P.ctr = c->ctr;
     const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)d.grid, (n + kWG - 1) / kWG));
-    HIP_OK(hipEventRecord(c.ev0, (hipStream_t)stream));
-    hipLaunchKernelGGL(surface_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, P, d_o, d_d, d_hits, n,
-                       hit_id_count(S), (const SurfaceGroup*)d.sgroups, (int32_t)d.n_sgroups, d_out);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(c.ev1, (hipStream_t)stream));
-    d.last = &c;
+    hipLaunchKernelGGL(surface_kernel, dim3(grid), dim3(kWG), 0, stream, P, d_o, d_d, d_hits, n, hit_id_count(S),
+                       (const SurfaceGroup*)d.sgroups, (int32_t)d.n_sgroups, d_out);
+    if ((rc = end_launch(d, *c, stream))) return rc;
     S.last = mrt_stats{};
     return MRT_OK;
 }
 
-int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n, mrt_surface* out) {
-    int rc = hit_surfaces_check(s, o, d, hits, n, out);
+int mrt_hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
+                           mrt_surface* d_out, void* stream) {
+    const int rc = ray_args_check(s, n, 0, {d_o, d_d, d_hits, d_out}, "ray / hit / output");
     if (rc || n == 0) return rc;
-    if ((rc = host_hits_check(s, hits, n))) return rc;
-    Scene& S = s->impl;
-    const int dev = S.dev ? S.dev->device : 0;
-    if ((rc = ensure_device(S, dev))) return rc;
-    HIP_OK(hipSetDevice(dev));
-    float *bo = nullptr, *bd = nullptr;
-    mrt_hit* bh = nullptr;
-    mrt_surface* bs = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void**)&bo, n * 12));
-        HIP_OK(hipMalloc((void**)&bd, n * 12));
-        HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
-        HIP_OK(hipMalloc((void**)&bs, n * sizeof(mrt_surface)));
-        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bh, hits, n * sizeof(mrt_hit), hipMemcpyHostToDevice));
-        int r = mrt_hit_surfaces_async(s, bo, bd, bh, n, bs, nullptr);
-        if (r) return r;
-        HIP_OK(hipMemcpy(out, bs, n * sizeof(mrt_surface), hipMemcpyDeviceToHost));
-        return MRT_OK;
-    };
-    rc = run();
-    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bh); (void)hipFree(bs);
-    return rc;
+    return hit_surfaces_async(s, d_o, d_d, d_hits, n, d_out, (hipStream_t)stream);
 }
 
-int mrt_sample_rays(mrt_scene* s, const float* o, const float* d, const float* time, size_t n, int32_t row_width,
-                    uint32_t seed, int32_t count_visits, float* rgb, mrt_hit* hits) {
-    int rc = sample_rays_check(s, o, d, n, row_width, rgb);
+int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit* hits, size_t n, mrt_surface* out) {
+    int rc = ray_args_check(s, n, 0, {o, d, hits, out}, "ray / hit / output");
     if (rc || n == 0) return rc;
-    Scene& S = s->impl;
-    const int dev = S.dev ? S.dev->device : 0;
-    if ((rc = ensure_device(S, dev))) return rc;
-    HIP_OK(hipSetDevice(dev));
-    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *brgb = nullptr;
-    mrt_hit* bh = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void**)&bo, n * 12));
-        HIP_OK(hipMalloc((void**)&bd, n * 12));
-        HIP_OK(hipMalloc((void**)&brgb, n * 12));
-        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
-        if (hits) HIP_OK(hipMalloc((void**)&bh, n * sizeof(mrt_hit)));
-        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
-        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
-        int r = mrt_sample_rays_async(s, bo, bd, bt, n, row_width, seed, count_visits, brgb, bh, nullptr);
-        if (r) return r;
-        HIP_OK(hipMemcpy(rgb, brgb, n * 12, hipMemcpyDeviceToHost));
-        if (hits) HIP_OK(hipMemcpy(hits, bh, n * sizeof(mrt_hit), hipMemcpyDeviceToHost));
-        mrt_stats tmp;
-        return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
-    };
-    rc = run();
-    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(brgb); (void)hipFree(bh);
-    return rc;
+    if ((rc = host_hits_check(s, hits, n))) return rc;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(s->impl, dp))) return rc;
+    Staged st;
+    const float *bo = st.in(o, n * 12), *bd = st.in(d, n * 12);
+    const mrt_hit* bh = st.in(hits, n * sizeof(mrt_hit));
+    mrt_surface* bs = st.out<mrt_surface>(n * sizeof(mrt_surface));
+    if (st.rc) return st.rc;
+    if ((rc = hit_surfaces_async(s, bo, bd, bh, n, bs, nullptr))) return rc;
+    return st.back(out, bs, n * sizeof(mrt_surface));   // no counters: the host check has refused every bad record
 }
 
 int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32_t seed, float* o, float* d, float* time) {
@@ -1915,7 +1912,7 @@ int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32
     int rc = host_camera(cam, width, height, C);   // (rejects a non-positive size)
     if (rc) return rc;
     const uint16_t* RS = host_rsqrt_table();
-    const uint32_t sd = seed ? seed : 0x5EEDu;
+    const uint32_t sd = seed_or_default(seed);
     for (int y = 0; y < height; y++)
         for (int x = 0; x < width; x++) {
             const EyeRay er = camera_ray(C, sd, x, y, RS);   // the device's eye_ray(), compiled for the host
@@ -2007,111 +2004,82 @@ int mrt_scene_last_stats(const mrt_scene* cs, mrt_stats* out) {
 
 // mrt_trace_async / mrt_trace_rays_async: d_time == nullptr is Ray(o, d), trace_kernel
 static int trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
-                       const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream) {
+                       const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, hipStream_t stream) {
+    int rc;
     Scene& S = s->impl;
-    int dev = S.dev ? S.dev->device : 0;
-    int rc = ensure_device(S, dev);
-    if (rc) return rc;
-    HIP_OK(hipSetDevice(dev));
-    DeviceState& d = *S.dev;
-    if (n == 0) return MRT_OK;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(S, dp)) || n == 0) return rc;
+    DeviceState& d = *dp;
     StreamCtx* cp = nullptr;
-    if ((rc = get_ctx(d, (hipStream_t)stream, cp))) return rc;
+    if ((rc = begin_query(S, d, stream, CTR_N * sizeof(unsigned long long), false, cp))) return rc;
     StreamCtx& c = *cp;
-    S.stats_final = false;
-    HIP_OK(hipMemsetAsync(c.ctr, 0, CTR_N * sizeof(unsigned long long), (hipStream_t)stream));
-    c.last_was_render = false;
-    c.supplied = false;
     int grid = (int)std::min<size_t>((size_t)d.grid, (n + kWG - 1) / kWG);
-    HIP_OK(hipEventRecord(c.ev0, (hipStream_t)stream));
     Trav alpha{};
     alpha.aprims = d.prims; alpha.apuv = d.puv; alpha.auv = d.uvs; alpha.amats = d.mats; alpha.atex = d.texs;
     alpha.pflags = d.pflags; alpha.verts = d.verts; alpha.verts2 = d.verts2;
     if (d_time) {
         auto kern = any_hit ? (d.special ? trace_timed_kernel<true, true> : trace_timed_kernel<true, false>)
                             : (d.special ? trace_timed_kernel<false, true> : trace_timed_kernel<false, false>);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, d.nodes, d.leaves, d.tables, c.gstack,
-                           d.gthreads, d_o, d_d, d_time, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, stream, d.nodes, d.leaves, d.tables, c.gstack, d.gthreads,
+                           d_o, d_d, d_time, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
     } else {
         auto kern = any_hit ? (d.special ? trace_kernel<true, true> : trace_kernel<true, false>)
                             : (d.special ? trace_kernel<false, true> : trace_kernel<false, false>);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, d.nodes, d.leaves, d.tables, c.gstack,
-                           d.gthreads, d_o, d_d, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, stream, d.nodes, d.leaves, d.tables, c.gstack, d.gthreads,
+                           d_o, d_d, d_tmin, d_tmax, n, d_out, c.ctr, fast_box(d), d.insts, alpha);
     }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(c.ev1, (hipStream_t)stream));
-    d.last = &c;
-    return MRT_OK;
-}
-
-int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin, const float* d_tmax, size_t n,
-                    int any_hit, mrt_hit* d_out, void* stream) {
-    if (!s || (n && (!d_o || !d_d || !d_tmin || !d_tmax || !d_out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
-    return trace_async(s, d_o, d_d, nullptr, d_tmin, d_tmax, n, any_hit, d_out, stream);
-}
-
-// ---- Scene::trace for rays with a time (mrt_trace_rays): the argument checks of both entries
-static int trace_rays_check(const mrt_scene* s, const float* o, const float* d, const float* tmin, const float* tmax,
-                            size_t n, const mrt_hit* out) {
-    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
-    if (n && (!o || !d || !tmin || !tmax || !out)) { set_error("null ray / bound / output array"); return MRT_ERR_INVALID; }
-    if (n > kMaxRayBatch) { set_error("at most 2^28 rays per batch"); return MRT_ERR_INVALID; }
-    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
-    return MRT_OK;
-}
-
-int mrt_trace_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
-                         const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream) {
-    const int rc = trace_rays_check(s, d_o, d_d, d_tmin, d_tmax, n, d_out);
-    if (rc || n == 0) return rc;
-    return trace_async(s, d_o, d_d, d_time, d_tmin, d_tmax, n, any_hit, d_out, stream);
+    return end_launch(d, c, stream);
 }
 
 // mrt_trace / mrt_trace_rays: host arrays in and out (time nullable)
 static int trace_sync(mrt_scene* s, const float* o, const float* d, const float* time, const float* tmin,
                       const float* tmax, size_t n, int any_hit, mrt_hit* out) {
-    Scene& S = s->impl;
-    int dev = S.dev ? S.dev->device : 0;
-    int rc = ensure_device(S, dev);
-    if (rc) return rc;
-    if (n == 0) return MRT_OK;
-    HIP_OK(hipSetDevice(dev));
-    float *bo = nullptr, *bd = nullptr, *bt = nullptr, *bmin = nullptr, *bmax = nullptr;
-    mrt_hit* bout = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void**)&bo, n * 12));
-        HIP_OK(hipMalloc((void**)&bd, n * 12));
-        if (time) HIP_OK(hipMalloc((void**)&bt, n * 4));
-        HIP_OK(hipMalloc((void**)&bmin, n * 4));
-        HIP_OK(hipMalloc((void**)&bmax, n * 4));
-        HIP_OK(hipMalloc((void**)&bout, n * sizeof(mrt_hit)));
-        HIP_OK(hipMemcpy(bo, o, n * 12, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bd, d, n * 12, hipMemcpyHostToDevice));
-        if (time) HIP_OK(hipMemcpy(bt, time, n * 4, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bmin, tmin, n * 4, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bmax, tmax, n * 4, hipMemcpyHostToDevice));
-        int r = trace_async(s, bo, bd, bt, bmin, bmax, n, any_hit, bout, nullptr);
-        if (r) return r;
-        HIP_OK(hipMemcpy(out, bout, n * sizeof(mrt_hit), hipMemcpyDeviceToHost));
-        unsigned long long c[CTR_N];
-        HIP_OK(hipMemcpy(c, S.dev->last->ctr, sizeof c, hipMemcpyDeviceToHost));
-        if (c[CTR_OVERFLOW]) { set_error("traversal stack overflow"); return MRT_ERR_OVERFLOW; }
-        return MRT_OK;
-    };
-    rc = run();
-    (void)hipFree(bo); (void)hipFree(bd); (void)hipFree(bt); (void)hipFree(bmin); (void)hipFree(bmax); (void)hipFree(bout);
-    return rc;
+    int rc;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(s->impl, dp)) || n == 0) return rc;
+    Staged st;
+    const float *bo = st.in(o, n * 12), *bd = st.in(d, n * 12), *bt = st.in(time, n * 4);
+    const float *bmin = st.in(tmin, n * 4), *bmax = st.in(tmax, n * 4);
+    mrt_hit* bout = st.out<mrt_hit>(n * sizeof(mrt_hit));
+    if (st.rc) return st.rc;
+    if ((rc = trace_async(s, bo, bd, bt, bmin, bmax, n, any_hit, bout, nullptr))) return rc;
+    if ((rc = st.back(out, bout, n * sizeof(mrt_hit)))) return rc;
+    unsigned long long c[CTR_N];   // only the overflow flag: a trace leaves the scene's last statistics alone
+    if ((rc = st.back(c, dp->last->ctr, sizeof c))) return rc;
+    if (c[CTR_OVERFLOW]) { set_error("traversal stack overflow"); return MRT_ERR_OVERFLOW; }
+    return MRT_OK;
+}
+
+// The older pair keeps its own checks: one message, no batch cap, and "not built" comes from the
+// replica, so n == 0 asks for it too.
+static int trace_args_check(const mrt_scene* s, size_t n, std::initializer_list<const void*> need) {
+    if (!s || (n && any_null(need))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    return MRT_OK;
+}
+
+int mrt_trace_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_tmin, const float* d_tmax, size_t n,
+                    int any_hit, mrt_hit* d_out, void* stream) {
+    if (const int rc = trace_args_check(s, n, {d_o, d_d, d_tmin, d_tmax, d_out})) return rc;
+    return trace_async(s, d_o, d_d, nullptr, d_tmin, d_tmax, n, any_hit, d_out, (hipStream_t)stream);
 }
 
 int mrt_trace(mrt_scene* s, const float* o, const float* d, const float* tmin, const float* tmax, size_t n, int any_hit,
               mrt_hit* out) {
-    if (!s || (n && (!o || !d || !tmin || !tmax || !out))) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    if (const int rc = trace_args_check(s, n, {o, d, tmin, tmax, out})) return rc;
     return trace_sync(s, o, d, nullptr, tmin, tmax, n, any_hit, out);
+}
+
+// ---- Scene::trace for rays with a time (mrt_trace_rays)
+int mrt_trace_rays_async(mrt_scene* s, const float* d_o, const float* d_d, const float* d_time, const float* d_tmin,
+                         const float* d_tmax, size_t n, int any_hit, mrt_hit* d_out, void* stream) {
+    const int rc = ray_args_check(s, n, 0, {d_o, d_d, d_tmin, d_tmax, d_out}, "ray / bound / output");
+    if (rc || n == 0) return rc;
+    return trace_async(s, d_o, d_d, d_time, d_tmin, d_tmax, n, any_hit, d_out, (hipStream_t)stream);
 }
 
 int mrt_trace_rays(mrt_scene* s, const float* o, const float* d, const float* time, const float* tmin, const float* tmax,
                    size_t n, int any_hit, mrt_hit* out) {
-    const int rc = trace_rays_check(s, o, d, tmin, tmax, n, out);
+    const int rc = ray_args_check(s, n, 0, {o, d, tmin, tmax, out}, "ray / bound / output");
     if (rc || n == 0) return rc;
     return trace_sync(s, o, d, time, tmin, tmax, n, any_hit, out);
 }
@@ -2142,30 +2110,17 @@ int mrt_debug_libm(int fn, const float* x, const float* y, size_t n, float* out)
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device"); return MRT_ERR_NO_DEVICE; }
     if (n == 0) return MRT_OK;
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    uint16_t* dt = nullptr;
     const size_t b = n * sizeof(float);
-    int rc = MRT_OK;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void**)&dx, b));
-        HIP_OK(hipMalloc((void**)&dy, b));
-        HIP_OK(hipMalloc((void**)&dout, b));
-        HIP_OK(hipMalloc((void**)&dt, 2048 * sizeof(uint16_t)));
-        HIP_OK(hipMemcpy(dx, x, b, hipMemcpyHostToDevice));
-        if (fn == 1 || fn == 5) HIP_OK(hipMemcpy(dy, y, b, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dt, host_rcp_table(), 2048 * sizeof(uint16_t), hipMemcpyHostToDevice));
-        const int blocks = (int)std::min<size_t>((n + 255) / 256, 65536);
-        hipLaunchKernelGGL(libm_kernel, dim3(blocks), dim3(256), 0, 0, fn, dx, dy, n, dout, dt);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(out, dout, b, hipMemcpyDeviceToHost));
-        return MRT_OK;
-    };
-    rc = run();
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    if (dout) (void)hipFree(dout);
-    if (dt) (void)hipFree(dt);
-    return rc;
+    Staged st;
+    const float* dx = st.in(x, b);
+    const float* dy = fn == 1 || fn == 5 ? st.in(y, b) : st.out<float>(b);   // (the kernel's argument; read by 1 and 5 only)
+    const uint16_t* dt = st.in(host_rcp_table(), 2048 * sizeof(uint16_t));
+    float* dout = st.out<float>(b);
+    if (st.rc) return st.rc;
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 65536);
+    hipLaunchKernelGGL(libm_kernel, dim3(blocks), dim3(256), 0, 0, fn, dx, dy, n, dout, dt);
+    HIP_OK(hipGetLastError());
+    return st.back(out, dout, b);
 }
 
 }  // extern "C"

@@ -486,6 +486,61 @@ class ProxyObject:
         bvh.objects = objects
 
 
+def _ptr(x):
+    """The address of a numpy array or a torch tensor; None stays None."""
+    if x is None:
+        return None
+    return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data
+
+
+class _RayQuery:
+    """What Scene's ray queries share: the checks of Scene._pairs, the scene on its device, and
+    the marshalling -- numpy arrays (made contiguous float32) go through the synchronous entry,
+    checked torch tensors through its _async twin on the current stream.  o, d, time, hits
+    are the inputs' addresses (None where there is none)."""
+
+    def __init__(self, scene, what, o, d, time=None, hits=None):
+        self.scene, self.what = scene, what
+        self.shape, self.n, self.tensors = scene._pairs(what, o, d, time, hits)
+        check(lib().mrt_scene_upload(scene.handle, scene.device), "upload")
+        if self.tensors:
+            import torch
+            self._device = o.device
+            self._stream = torch.cuda.current_stream(o.device).cuda_stream
+        else:
+            o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+            time = np.ascontiguousarray(time, np.float32) if time is not None else None
+            hits = np.ascontiguousarray(hits) if hits is not None else None
+        self._inputs = (o, d, time, hits)   # (the contiguous copies live as long as their addresses)
+        self.o, self.d, self.time, self.hits = map(_ptr, self._inputs)
+
+    def row_width(self, row_width):
+        """The coherence hint's default: W for an (H, W, 3) input, else 0."""
+        if row_width is None:
+            return self.shape[1] if len(self.shape) == 3 else 0
+        return int(row_width)
+
+    def new(self, dtype=None, words=None):
+        """An output: float rgb in the rays' shape, or one record per ray -- a `dtype` array of the
+        rays' shape, for tensors (n, words) int32."""
+        if self.tensors:
+            import torch
+            if dtype is None:
+                return torch.empty(self.shape, dtype=torch.float32, device=self._device)
+            return torch.empty((self.n, words), dtype=torch.int32, device=self._device)
+        return np.zeros(self.shape, np.float32) if dtype is None else np.zeros(self.shape[:-1], dtype)
+
+    def call(self, entry, *args, stats=False):
+        """entry(scene, *args), or entry_async(scene, *args, stream); stats: the synchronous
+        entry has read the counters, so Scene.last_stats follows."""
+        if self.tensors:
+            check(getattr(lib(), entry + "_async")(self.scene.handle, *args, self._stream), self.what)
+            return
+        check(getattr(lib(), entry)(self.scene.handle, *args), self.what)
+        if stats:
+            self.scene.last_stats = self.scene.stats()
+
+
 class Scene:
     """Scene (src/Scene.h).  Objects are whole meshes here; object ids inside a
     HitInfo are global triangle indices in insertion order."""
@@ -902,44 +957,15 @@ class Scene:
         default W for an (H, W, 3) input, else 0.  Returns rgb in the input's shape -- and the
         primary hit records (HIT_DTYPE; an (n, 5) int32 device tensor of t, a, b bits, prim,
         inst for tensors) when want_hits.  Ray i draws from RNG stream i of `seed`."""
-        L = lib()
-        shape = tuple(o.shape)
-        if len(shape) not in (2, 3) or shape[-1] != 3 or tuple(d.shape) != shape:
-            raise MRTError("sampleRays: o and d must both be (n, 3) or (H, W, 3)")
-        n = int(np.prod(shape[:-1]))
-        if time is not None and int(np.prod(tuple(time.shape))) != n:
-            raise MRTError("sampleRays: time must hold one value per ray")
-        if row_width is None:
-            row_width = shape[1] if len(shape) == 3 else 0
-        check(L.mrt_scene_upload(self.handle, self.device), "upload")
-        if hasattr(o, "data_ptr"):   # torch device tensors: enqueue on the current stream
-            import torch
-            ts = [o, d] + ([time] if time is not None else [])
-            for x in ts:
-                if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.device.index == self.device):
-                    raise MRTError("sampleRays: tensors must be contiguous float32 on the scene's device")
-            rgb = torch.empty(shape, dtype=torch.float32, device=o.device)
-            hits = torch.empty((n, 5), dtype=torch.int32, device=o.device) if want_hits else None
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            check(L.mrt_sample_rays_async(self.handle, o.data_ptr(), d.data_ptr(),
-                                          time.data_ptr() if time is not None else None, n, int(row_width), int(seed),
-                                          int(count_visits), rgb.data_ptr(), hits.data_ptr() if want_hits else None,
-                                          stream), "sampleRays")
-            return (rgb, hits) if want_hits else rgb
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        t = np.ascontiguousarray(time, np.float32) if time is not None else None
-        rgb = np.zeros(shape, np.float32)
-        hits = np.zeros(shape[:-1], HIT_DTYPE) if want_hits else None
-        check(L.mrt_sample_rays(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None, n,
-                                int(row_width), int(seed), int(count_visits), rgb.ctypes.data,
-                                hits.ctypes.data if want_hits else None), "sampleRays")
-        self.last_stats = self.stats()
+        q = _RayQuery(self, "sampleRays", o, d, time)
+        rgb, hits = q.new(), q.new(HIT_DTYPE, 5) if want_hits else None
+        q.call("mrt_sample_rays", q.o, q.d, q.time, q.n, q.row_width(row_width), int(seed), int(count_visits), _ptr(rgb),
+               _ptr(hits), stats=True)
         return (rgb, hits) if want_hits else rgb
 
     # -- assemble sampleScene yourself: trace (with ray times), edit or filter the hits, shade them
     def _pairs(self, what, o, d, time=None, hits=None):
-        """Shape checks shared by traceRays / shadeHits / hitSurfaces: (shape, n, tensors?)."""
+        """Shape checks shared by the ray queries: (shape, n, tensors?)."""
         shape = tuple(o.shape)
         if len(shape) not in (2, 3) or shape[-1] != 3 or tuple(d.shape) != shape:
             raise MRTError(f"{what}: o and d must both be (n, 3) or (H, W, 3)")
@@ -968,10 +994,9 @@ class Scene:
         reference's epsilon and MIRO_TMAX, the bounds of a camera ray).  numpy in: a HIT_DTYPE
         array of the rays' shape; torch device tensors: mrt_trace_rays_async on the current
         stream, an (n, 5) int32 tensor (t, a, b bits, prim, inst)."""
-        L = lib()
-        shape, n, tensors = self._pairs("traceRays", o, d, time)
-        check(L.mrt_scene_upload(self.handle, self.device), "upload")
-        if tensors:
+        q = _RayQuery(self, "traceRays", o, d, time)
+        n = q.n
+        if q.tensors:
             import torch
 
             def bound(x):
@@ -981,21 +1006,12 @@ class Scene:
             lo, hi = bound(tmin), bound(tmax)
             if lo.numel() != n or hi.numel() != n:
                 raise MRTError("traceRays: tmin / tmax must be scalars or hold one value per ray")
-            out = torch.empty((n, 5), dtype=torch.int32, device=o.device)
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            check(L.mrt_trace_rays_async(self.handle, o.data_ptr(), d.data_ptr(),
-                                         time.data_ptr() if time is not None else None, lo.data_ptr(), hi.data_ptr(),
-                                         n, int(any_hit), out.data_ptr(), stream), "traceRays")
-            return out   # (lo / hi were made on this stream: the allocator frees them in its order)
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        t = np.ascontiguousarray(time, np.float32) if time is not None else None
-        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32).reshape(-1), (n,)))
-        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32).reshape(-1), (n,)))
-        out = np.zeros(shape[:-1], HIT_DTYPE)
-        check(L.mrt_trace_rays(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None,
-                               lo.ctypes.data, hi.ctypes.data, n, int(any_hit), out.ctypes.data), "traceRays")
-        return out
+        else:
+            lo = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32).reshape(-1), (n,)))
+            hi = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32).reshape(-1), (n,)))
+        out = q.new(HIT_DTYPE, 5)
+        q.call("mrt_trace_rays", q.o, q.d, q.time, _ptr(lo), _ptr(hi), n, int(any_hit), _ptr(out))
+        return out   # (tensors lo / hi were made on this stream: the allocator frees them in its order)
 
     def shadeHits(self, o, d, hits, time=None, seed=0, count_visits=False, row_width=None):
         """The hit / miss branch of Scene::sampleScene for caller (ray, hit) pairs
@@ -1005,29 +1021,10 @@ class Scene:
         bad record); torch: an (n, 5) int32 device tensor on the current stream, bad records
         shaded as misses and reported by stats() as MRT_ERR_INVALID.  Returns rgb in the
         rays' shape."""
-        L = lib()
-        shape, n, tensors = self._pairs("shadeHits", o, d, time, hits)
-        if row_width is None:
-            row_width = shape[1] if len(shape) == 3 else 0
-        check(L.mrt_scene_upload(self.handle, self.device), "upload")
-        if tensors:
-            import torch
-            rgb = torch.empty(shape, dtype=torch.float32, device=o.device)
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            check(L.mrt_shade_hits_async(self.handle, o.data_ptr(), d.data_ptr(),
-                                         time.data_ptr() if time is not None else None, hits.data_ptr(), n,
-                                         int(row_width), int(seed), int(count_visits), rgb.data_ptr(), stream),
-                  "shadeHits")
-            return rgb
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        t = np.ascontiguousarray(time, np.float32) if time is not None else None
-        h = np.ascontiguousarray(hits)
-        rgb = np.zeros(shape, np.float32)
-        check(L.mrt_shade_hits(self.handle, o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None,
-                               h.ctypes.data, n, int(row_width), int(seed), int(count_visits), rgb.ctypes.data),
-              "shadeHits")
-        self.last_stats = self.stats()
+        q = _RayQuery(self, "shadeHits", o, d, time, hits)
+        rgb = q.new()
+        q.call("mrt_shade_hits", q.o, q.d, q.time, q.hits, q.n, q.row_width(row_width), int(seed), int(count_visits),
+               _ptr(rgb), stats=True)
         return rgb
 
     def hitSurfaces(self, o, d, hits):
@@ -1036,22 +1033,9 @@ class Scene:
         mesh, tri, inst; zeros and -1 for a miss.  torch device tensors: the current stream,
         an (n, 21) int32 tensor of the same words (floats as bits;
         x.cpu().numpy().view(SURFACE_DTYPE) names them)."""
-        L = lib()
-        shape, n, tensors = self._pairs("hitSurfaces", o, d, None, hits)
-        check(L.mrt_scene_upload(self.handle, self.device), "upload")
-        if tensors:
-            import torch
-            out = torch.empty((n, 21), dtype=torch.int32, device=o.device)
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            check(L.mrt_hit_surfaces_async(self.handle, o.data_ptr(), d.data_ptr(), hits.data_ptr(), n, out.data_ptr(),
-                                           stream), "hitSurfaces")
-            return out
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        h = np.ascontiguousarray(hits)
-        out = np.zeros(shape[:-1], SURFACE_DTYPE)
-        check(L.mrt_hit_surfaces(self.handle, o.ctypes.data, d.ctypes.data, h.ctypes.data, n, out.ctypes.data),
-              "hitSurfaces")
+        q = _RayQuery(self, "hitSurfaces", o, d, None, hits)
+        out = q.new(SURFACE_DTYPE, 21)
+        q.call("mrt_hit_surfaces", q.o, q.d, q.hits, q.n, _ptr(out))
         return out
 
     def primObject(self, prim: int):

@@ -77,6 +77,20 @@ def test_atan2f_pairs(harness):
     assert out.returncode == 0, out.stdout
 
 
+def test_probe_argument_checks_come_before_any_device_call():
+    """mrt_debug_libm: fn out of range, a null x or out, a null y for the two-argument
+    functions (1 atan2, 5 pow) -- MRT_ERR_INVALID, on a host without a device too."""
+    L = miro.lib()
+    buf = np.zeros(4, np.float32)
+    p = buf.ctypes.data
+    for fn, x, y, out in ((-1, p, p, p), (6, p, p, p), (0, None, p, p), (0, p, p, None), (1, p, None, p),
+                          (5, p, None, p)):
+        assert L.mrt_debug_libm(fn, x, y, 4, out) == -1, (fn, x, y, out)
+        assert L.mrt_last_error().decode() == "bad libm probe arguments"
+    if miro.device_count() < 1:   # one argument: y is not needed; the next stop is the device
+        assert L.mrt_debug_libm(0, p, None, 4, p) == -7
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fn", ["acos", "atan2", "sin", "cos", "pow"])
 def test_device_libm_equals_glibc(fn):

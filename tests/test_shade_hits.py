@@ -6,8 +6,9 @@ The defining property: for the rays of mrt_camera_rays, the closest hits of
 mrt_trace_rays(o, d, time, tmin = 0.001, tmax = 1e12) are the hit records of mrt_sample_rays
 byte for byte, and mrt_shade_hits on them is its float RGB bit for bit, with the same ray
 counts -- on every dispatch path of the engine, the scene list of tests/test_sample_rays.py.
-CPU tests cover the argument checks of all six entries and the host validation of hit
-records.  Frames are 37 x 29: neither 8, 64 nor a row width divides evenly."""
+CPU tests cover the argument checks of all six entries, those the older mrt_trace pair keeps,
+and the host validation of hit records.  Frames are 37 x 29: neither 8, 64 nor a row width
+divides evenly.  One GPU test holds every synchronous entry against its async twin."""
 import ctypes as C
 
 import numpy as np
@@ -77,6 +78,41 @@ def test_argument_checks_come_before_any_device_call(entry):
         assert call(raw, p, p, p, p, 1) == -5 and "not built" in last_error()
     finally:
         L.mrt_scene_destroy(raw)
+
+
+@pytest.mark.parametrize("entry", ["mrt_trace", "mrt_trace_async"])
+def test_untimed_trace_keeps_its_own_argument_checks(entry):
+    """mrt_trace / mrt_trace_async, the older pair: "bad argument" for a null scene or array, no
+    2^28 cap (such a batch passes the checks and, on a host without a device, stops at the
+    upload), and n == 0 still asks for the replica first: "not built" on an unbuilt scene."""
+    L = miro.lib()
+    P = built_scene()
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data
+    f = getattr(L, entry)
+    tail = (None,) if entry.endswith("async") else ()
+
+    def call(s, o, d, tmin, tmax, out, n):
+        if not tail:   # mrt_trace declares its four inputs float*
+            o, d, tmin, tmax = (x and C.cast(x, C.POINTER(C.c_float)) for x in (o, d, tmin, tmax))
+        return f(s, o, d, tmin, tmax, n, 0, out, *tail)
+
+    assert call(None, p, p, p, p, p, 1) == -1 and last_error() == "bad argument"
+    for k in range(5):
+        a = [p] * 5
+        a[k] = None
+        L.mrt_scene_upload(None, 0)   # another text in between: "null scene"
+        assert call(P.handle, *a, 1) == -1 and last_error() == "bad argument", k
+    raw = L.mrt_scene_create()   # no BVH yet
+    try:
+        for n in (0, 1):
+            assert call(raw, p, p, p, p, p, n) == -5 and "not built" in last_error(), n
+        assert call(raw, None, None, None, None, None, 0) == -5 and "not built" in last_error()
+    finally:
+        L.mrt_scene_destroy(raw)
+    if miro.device_count() < 1:   # past the checks: the next stop is the device
+        assert call(P.handle, p, p, p, p, p, (1 << 28) + 1) == -7 and "no HIP device" in last_error()
+        assert call(P.handle, None, None, None, None, None, 0) == -7
 
 
 # ------------------------------------------------------------------ CPU: the host validation of hit records
@@ -366,3 +402,48 @@ def test_async_bad_ids_are_shaded_as_misses_and_reported_by_last_stats():
         P.shadeHits(to, td, hit_tensor(hits, dev), tt, seed=4)
     side.synchronize()
     assert miro.lib().mrt_scene_last_stats(P.handle, C.byref(st)) == 0
+
+
+@pytest.mark.gpu
+def test_every_synchronous_entry_equals_its_async_twin():
+    """The five host-array entries against their device-array twins, bit for bit, with and
+    without a time array, at n = 1 and n = 65: one ray more than a 64-ray work item, an odd
+    tail of the 256-thread record kernels."""
+    need_gpu()
+    import torch
+    L = miro.lib()
+    P = built_scene()
+    dev = torch.device("cuda", P.device)
+    ro, rd, rt = (x.reshape(-1, *x.shape[2:]) for x in camera(dict(CAM, shutterSpeed=0.25)).rays(W, H, 9))
+    for n in (1, 65):
+        o, d = np.ascontiguousarray(ro[:n]), np.ascontiguousarray(rd[:n])
+        to, td = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+        # mrt_trace has no tensor wrapper: its twin through the C ABI, on the current stream
+        lo, hi = torch.full((n,), 0.001, device=dev), torch.full((n,), 1e12, device=dev)
+        out = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        assert L.mrt_trace_async(P.handle, to.data_ptr(), td.data_ptr(), lo.data_ptr(), hi.data_ptr(), n, 0,
+                                 out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream) == 0
+        plain = P.traceBatch(o, d)
+        assert out.cpu().numpy().tobytes() == plain.tobytes(), n
+        for t in (None, np.ascontiguousarray(rt[:n])):
+            tt = None if t is None else torch.from_numpy(t).to(dev)
+            what = (n, t is not None)
+            hits = P.traceRays(o, d, t)
+            th = P.traceRays(to, td, tt)
+            assert th.cpu().numpy().tobytes() == hits.tobytes(), what
+            if t is None:
+                assert hits.tobytes() == plain.tobytes(), n
+            rgb, shits = P.sampleRays(o, d, t, seed=9, want_hits=True)
+            assert P.stats()["primary_rays"] == n, what
+            trgb, tshits = P.sampleRays(to, td, tt, seed=9, want_hits=True)
+            assert np.array_equal(bits(trgb.cpu().numpy()), bits(rgb)), what
+            assert tshits.cpu().numpy().tobytes() == shits.tobytes() == hits.tobytes(), what
+            assert P.stats()["primary_rays"] == n, what
+            shaded = P.shadeHits(o, d, hits, t, seed=9)
+            assert P.stats()["primary_rays"] == n and np.array_equal(bits(shaded), bits(rgb)), what
+            tshaded = P.shadeHits(to, td, th, tt, seed=9)
+            assert np.array_equal(bits(tshaded.cpu().numpy()), bits(shaded)), what
+            assert P.stats()["primary_rays"] == n, what
+        surf = P.hitSurfaces(o, d, plain)
+        tsurf = P.hitSurfaces(to, td, hit_tensor(plain, dev))
+        assert surf.shape == (n,) and tsurf.cpu().numpy().tobytes() == surf.tobytes(), n
