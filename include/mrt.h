@@ -685,6 +685,10 @@ int mrt_device_wall_clock_khz(const mrt_scene* s);
  * restated, csrc/mrt_libm.h), or its rcp_nr(x) (fn 2: the RCPSS emulation and Newton step
  * of every triangle test; y unused). */
 int mrt_debug_libm(int fn, const float* x, const float* y, size_t n, float* out);
+/* Ownership probe: the device allocations, pinned allocations, events and streams the library's
+ * replicas, stream contexts and staging buffers hold in this process now.  It returns to its
+ * earlier value when what was created since has been destroyed (mrt_scene_destroy). */
+int64_t mrt_debug_live_resources(void);
 float mrt_rcp_nr(float x);
 float mrt_rsqrt_nr(float x);
 

@@ -1,8 +1,13 @@
 // mrt_device.h -- internal (not installed): the tuning table, and the per-device /
-// per-stream state shared by mrt_upload.hip (upload, stream contexts) and
-// mrt_device.hip (launches).  host_api.cpp, plain C++, sees the tuning table only.
+// per-stream state shared by mrt_upload.hip (the owner, upload, stream contexts),
+// mrt_device.hip (launches) and mrt_refit.hip.  host_api.cpp, plain C++, sees the tuning table only.
+//
+// Memory: a DeviceState and each of its StreamCtx hold one DevOwner, the only code in csrc
+// that allocates or frees device memory, pinned memory, events and streams.  What an owner
+// made it frees when it dies; the typed pointer fields beside it are views for the kernels'
+// arguments.  Scratch that grows goes through reserve(): one group of buffers, one drain rule.
 #pragma once
-#include "mrt_scene.h"
+#include "mrt_image.h"
 
 namespace mrt {
 
@@ -80,20 +85,13 @@ struct Tuning {
 };
 extern Tuning g_tune;   // defined in host_api.cpp
 
-// The walks address a lane's node and leaf triangle as a 32-bit byte offset from the array's
-// base (node_at / tri_at, mrt_kernels.h), so a device node array (128 B per node) and leaf
-// array (160 B per packet) must each end within 4 GiB.  Upload refuses a scene past that
-// (MRT_ERR_OVERFLOW; mrt_walk_arrays_fit, host_api.cpp, is the same test on the C-ABI).
-inline bool walk_arrays_fit(uint64_t n_nodes, uint64_t n_leaves) {
-    return n_nodes <= (uint64_t(1) << 32) / 128 && n_leaves <= (uint64_t(1) << 32) / 160;
-}
-
 }  // namespace mrt
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 
 namespace mrt {
@@ -107,13 +105,59 @@ namespace mrt {
         }                                                                               \
     } while (0)
 
+// ------------------------------------------------------------------ ownership
+// Records what it creates and frees it in free_all / its destructor: events and streams
+// first, then memory.  On failure the out-parameter stays as it was (null) and the HIP error
+// text is set (MRT_ERR_HIP).  The current device is the owner's whenever it is used.
+class DevOwner {
+public:
+    DevOwner() = default;
+    DevOwner(const DevOwner&) = delete;
+    DevOwner& operator=(const DevOwner&) = delete;
+    ~DevOwner() { free_all(); }
+    template <typename T> int alloc(T*& p, size_t bytes, bool pinned = false) {
+        void* q = nullptr;
+        const int rc = memory(q, bytes, pinned);
+        if (q) p = static_cast<T*>(q);
+        return rc;
+    }
+    template <typename T> int pinned(T*& p, size_t bytes) { return alloc(p, bytes, true); }
+    int event(hipEvent_t& ev, unsigned flags = hipEventDefault);
+    int stream(hipStream_t& st);   // non-blocking
+    // allocate (16 bytes for an empty array) and copy from the host, synchronously
+    template <typename T> int upload(T*& p, const void* src, size_t bytes) {
+        void* q = nullptr;
+        if (const int rc = alloc(q, bytes ? bytes : 16)) return rc;
+        p = static_cast<T*>(q);
+        if (bytes) HIP_OK(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice));
+        return MRT_OK;
+    }
+    void release(void* p);    // frees one recorded allocation and forgets it (null: nothing)
+    void free_all();
+    static int64_t live();    // what every owner of this process holds now (mrt_debug_live_resources)
+private:
+    struct Held { void* h; void (*destroy)(void*); bool memory; };
+    int memory(void*& p, size_t bytes, bool pinned);
+    void keep(void* h, void (*destroy)(void*), bool memory);
+    std::vector<Held> held;
+};
+
+// A group of scratch buffers that share capacity fields: grown, never shrunk.  When a capacity
+// falls short and a buffer of the group is live, `drain` (the stream whose launches may still
+// read it; nullptr: none) is synchronised; then the whole group is released and allocated
+// anew.  After a failed allocation the capacities stay 0, so the next call tries again.
+struct GrowBuf { void** ptr; size_t bytes; };
+struct GrowCap { size_t* cap; size_t need; };
+int reserve(DevOwner& own, const hipStream_t* drain, std::initializer_list<GrowBuf> bufs, std::initializer_list<GrowCap> caps);
+
 // ------------------------------------------------------------------ device state
 // Launch scratch of one stream: everything a render / trace launch writes
 // besides the caller's outputs.  Two launches on different streams never share
 // one, so frames can overlap (the tail of one persistent launch with the start
 // of the next).
 struct StreamCtx {
-    hipStream_t stream = nullptr;
+    DevOwner own;                            // its buffers and events
+    hipStream_t stream = nullptr;            // the caller's
     int32_t* gstack = nullptr;               // traversal-stack spill columns
     unsigned long long* ctr = nullptr;       // statistics + tile counters
     unsigned long long* wave_log = nullptr;  // 2 launches x grid x 4 waves x kLogWords u64 (diagnostics)
@@ -156,7 +200,7 @@ struct StreamCtx {
 };
 static constexpr int kMaxStreamCtx = 16;
 
-// persistent buffers of one bucket share of mrt_render over several devices
+// persistent buffers of one bucket share of mrt_render over several devices (owned by the replica)
 struct ShareBuf {
     int32_t* items = nullptr;
     float* tiles = nullptr;
@@ -169,20 +213,10 @@ struct ShareBuf {
 // (mrt_hit_surfaces: HitInfo::obj of a hit on the device).
 struct SurfaceGroup { int32_t start, mesh, tri0, step; };
 
-// One tree the refit walks, the world's or a BLAS's: where it lies in the replica's arrays (the
-// upload), and the schedule the first refit makes: its nodes in device numbers sorted by height.
-struct RefitTree {
-    uint32_t node_base = 0, n_nodes = 0;    // node_base is the root (BLAS nodes are not permuted; the world's are: node_perm)
-    uint32_t leaf_base = 0, n_leaves = 0;   // DLeaf packets leaf_base .. leaf_base + n_leaves - 1
-    int32_t shade_base = 0;                 // PrimShade of its object 0
-    bool fixed_lanes = false;               // the world: ProxyObject / MBObject lanes take their boxes from refit_fixed
-    const int32_t* order = nullptr;         // its part of DeviceState::refit_order
-    std::vector<uint32_t> off;              //   height h holds order[off[h] .. off[h + 1])
-};
-
-struct DeviceState {
+struct DeviceState : ImageInfo {
+    DevOwner own;                // every device array, scratch buffer, event and stream below but the contexts'
     int device = -1;
-    SurfaceGroup* sgroups = nullptr;   // built by the first mrt_hit_surfaces call on this replica (one of bufs)
+    SurfaceGroup* sgroups = nullptr;   // built by the first mrt_hit_surfaces call on this replica
     int n_sgroups = 0;
     QNode* nodes = nullptr;
     DLeaf* leaves = nullptr;
@@ -193,22 +227,17 @@ struct DeviceState {
     DevLight* lights = nullptr;
     DevDome* domes = nullptr;
     DevInstance* insts = nullptr;
-    int n_insts = 0, n_world = 0;
     int32_t* inst_hit_base = nullptr;   // per instance: hit_base (ascending), for the instance-major bin keys
     uint16_t* inst_class = nullptr;     //   and its 7-bit class (BLAS-major rank)
     float4* inst_cell = nullptr;        //   object-space bin cells: BLAS box lo + BLAS bit, 4 / extent (2 per instance)
-    DevTexture* texs = nullptr;   // material-map textures (bufs hold their data)
+    DevTexture* texs = nullptr;   // material-map textures
     uint4* puv = nullptr;         // per prim texture-coordinate indices (nullptr: no texture-mapped mesh)
     float2* uvs = nullptr;
     float4* tans = nullptr;       // per normal: tangent / bitangent (texture-mapped meshes)
     float4* btans = nullptr;
-    bool has_maps = false, has_alpha = false;
     uint8_t* pflags = nullptr;    // motion blur: per world prim bit 0 = MBObject lane
     float4* verts2 = nullptr;     //   time-1 vertices parallel to verts (copies of verts for static meshes)
-    bool has_mb = false;
-    bool special = false;         // instances, alpha maps or motion blur: leaf packets with special lanes (INST kernels)
-    std::vector<void*> bufs;     // textures and dome tables (freed with the state)
-    const float* env = nullptr;  // environment texture (one of bufs)
+    const float* env = nullptr;  // environment texture
     uint16_t* tables = nullptr;
     uint8_t* gamma = nullptr;
     float* gammaF = nullptr;
@@ -218,46 +247,21 @@ struct DeviceState {
     uint8_t* d_rgb8 = nullptr;
     size_t frame_px = 0;
     int grid = 0;                // upper bound of any launch (kMaxBlocksPerCU per CU)
-    bool boxes_finite = false;
-    bool boxes_ordered = false;  // every used slot box has lo <= hi per axis (octant-ordered box test)
-    bool lds_ok = false;         // the world hierarchy has kLdsNodes nodes for the LDS top-node walk (renumbered)
     std::atomic<int> lds_pick{-1};   // the last one-light frame ran the LDS top-node walk: 1 yes, 0 no, -1 none yet
-    float bb_lo[3] = {0, 0, 0}, bb_hi[3] = {0, 0, 0};   // world root box (ray-binning origin cells)
-    // refit (mrt_refit.hip): per mesh the first float4 of its slice of verts / normals, the
-    // world hierarchy and its canonical -> device node numbers (the LDS breadth-first
-    // permutation; empty = identity); the rest is made by the first refit on this replica
-    std::vector<uint32_t> vbase, nbase;
-    std::vector<int32_t> node_perm;
-    RefitTree world;                      // nodes, packets and PrimShade records from 0
+    // refit (mrt_refit.hip), made by the first refit on this replica
     bool refit_ready = false;
-    int32_t* refit_order = nullptr;       // device node numbers of the world, then of every BLAS, each sorted by height (one of bufs)
-    float4* refit_lbox = nullptr;         // per packet, world then BLASes, by device packet number: box min xyz, max xyz (2 float4; one of bufs)
+    int32_t* refit_order = nullptr;       // device node numbers of the world, then of every BLAS, each sorted by height
+    float4* refit_lbox = nullptr;         // per packet, world then BLASes, by device packet number: box min xyz, max xyz (2 float4)
     float4* refit_fixed = nullptr;        // ProxyObject lanes' boxes by instance, then MBObject lanes' (2 float4 each)
     int32_t* refit_mbslot = nullptr;      //   per world prim: its MBObject box after the instances', -1 = none
-    float* refit_inst_m = nullptr;        // per instance: m_transform, 16 floats (refit_instance_kernel keeps it current; one of bufs)
+    float* refit_inst_m = nullptr;        // per instance: m_transform, 16 floats (refit_instance_kernel keeps it current)
     float* refit_stage = nullptr;         // the synchronous entry's packed vertices / normals on the device
     size_t refit_stage_cap = 0;           //   floats
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
-    // mrt_scene_deform_mesh: where each BLAS lies in nodes / leaves / prims (the upload; its
-    // child words hold device node and packet numbers), and what the first refit adds: its
-    // tree's schedule and the ids of its instances
-    struct BlasRange {
-        RefitTree tree;
-        uint32_t inst_at = 0, n_inst = 0;      // refit_blas_insts[inst_at .. inst_at + n_inst): its instances, ascending
-    };
-    std::vector<BlasRange> blas;
-    uint32_t n_leaves_all = 0;             // packets of the world and every BLAS (refit_lbox holds them all)
-    int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS (one of bufs)
+    int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS
     std::vector<int32_t> mesh_prim0;       // per mesh: its first world prim (its triangles follow in order), -1 = none
     int cus = 0;
-    bool point_only = false;
-    bool dome = false;           // a dome light (incoherent shadow rays)
-    int recursive = 0;           // chain shading (Shader REC): 1 reflection / refraction, 2 + path tracing
-    bool disperse = false;       // a dispersive Blinn material with secondary rays: the fused (tree) engine
-    bool transparent = false;    // a rect / dome light with transparent shadows: fused kernels only
-    bool pow_spec = false;       // a Blinn material with specExp != 1 (frame1 / shade1 kernels with pow)
     int wall_khz = 0;            // wall_clock64() rate
-    size_t bytes = 0;
     // per-stream launch scratch: frames on different streams are in flight at once
     std::mutex mu;
     std::vector<StreamCtx*> ctxs;
@@ -274,7 +278,6 @@ struct DeviceState {
 void free_replicas(Scene& s);
 int get_ctx(DeviceState& d, hipStream_t stream, StreamCtx*& out);   // scratch context of `stream`
 int ensure_device(Scene& s, int device);                            // the scene's replica on `device` becomes s.dev
-void root_box(const QNode& root, float lo[3], float hi[3]);         // union of the root's used slot boxes (finite values)
 
 }  // namespace mrt
 #endif   // __HIPCC__

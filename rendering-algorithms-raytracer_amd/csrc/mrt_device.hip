@@ -1,6 +1,7 @@
 // mrt_device.hip -- kernels, launch logic and the device side of libmrt's C-ABI
-// (MI355X / gfx950).  The CPU-only entries are in host_api.cpp, the scene upload
-// and the per-stream contexts in mrt_upload.hip, their shared state in mrt_device.h.
+// (MI355X / gfx950).  The CPU-only entries are in host_api.cpp, the scene upload, the
+// per-stream contexts and the owner of all device memory in mrt_upload.hip, their shared
+// state in mrt_device.h.
 //
 // Render kernel: persistent workgroups of 4 waves; a wave renders one 8x8
 // pixel tile per step (one lane per pixel), so a wave's rays are coherent.
@@ -554,29 +555,9 @@ static int level_words(const Scene& s) {
     return s.dev && s.dev->disperse ? std::max(w, kDispWords) : w;
 }
 
-// A group of a stream context's scratch buffers that share capacity fields: grown,
-// never shrunk.  When a capacity falls short the stream is drained (its previous
-// launch may still read the buffers) and the whole group is freed and allocated
-// anew; after a failed allocation the capacities stay 0, so the next call tries again.
-struct GrowBuf { void** ptr; size_t bytes; };
-struct GrowCap { size_t* cap; size_t need; };
-static int grow(StreamCtx& c, std::initializer_list<GrowBuf> bufs, std::initializer_list<GrowCap> caps) {
-    bool enough = true;
-    for (const GrowCap& k : caps) enough &= k.need <= *k.cap;
-    if (enough) return MRT_OK;
-    HIP_OK(hipStreamSynchronize(c.stream));
-    for (const GrowBuf& b : bufs) {
-        if (*b.ptr) (void)hipFree(*b.ptr);
-        *b.ptr = nullptr;
-    }
-    for (const GrowCap& k : caps) *k.cap = 0;
-    for (const GrowBuf& b : bufs) HIP_OK(hipMalloc(b.ptr, b.bytes));
-    for (const GrowCap& k : caps) *k.cap = k.need;
-    return MRT_OK;
-}
-
+// Scratch groups of a stream context (reserve, mrt_device.h): its stream's last launch may still read them.
 static int ensure_levels(StreamCtx& c, size_t floats) {
-    return grow(c, {{(void**)&c.lvl, floats * sizeof(float)}}, {{&c.lvl_cap, floats}});
+    return reserve(c.own, &c.stream, {{(void**)&c.lvl, floats * sizeof(float)}}, {{&c.lvl_cap, floats}});
 }
 
 static inline int fast_box(const DeviceState& d) { return (g_tune.fast_box && d.boxes_finite) ? 1 : 0; }
@@ -584,14 +565,14 @@ static inline int fast_box(const DeviceState& d) { return (g_tune.fast_box && d.
 // wavefront shadow-ray buffers of a stream context
 static int ensure_rays(StreamCtx& c, size_t slots, size_t per_slot) {
     const size_t n = slots * per_slot;
-    return grow(c, {{(void**)&c.rays, 2 * n * sizeof(float4)}, {(void**)&c.occl, n}, {(void**)&c.nrays, slots}},
-                {{&c.ray_cap, n}, {&c.nrays_cap, slots}});
+    return reserve(c.own, &c.stream, {{(void**)&c.rays, 2 * n * sizeof(float4)}, {(void**)&c.occl, n}, {(void**)&c.nrays, slots}},
+                   {{&c.ray_cap, n}, {&c.nrays_cap, slots}});
 }
 
 // Dome-light replay scratch of a stream: n ray slots, calls call records.
 static int ensure_replay(StreamCtx& c, size_t n, size_t calls) {
-    return grow(c, {{(void**)&c.ray_e, n * sizeof(float4)}, {(void**)&c.lrec, calls * sizeof(uint32_t)}},
-                {{&c.ray_e_cap, n}, {&c.lrec_cap, calls}});
+    return reserve(c.own, &c.stream, {{(void**)&c.ray_e, n * sizeof(float4)}, {(void**)&c.lrec, calls * sizeof(uint32_t)}},
+                   {{&c.ray_e_cap, n}, {&c.lrec_cap, calls}});
 }
 
 // The binning switches in effect for a scene (tuning "bin", or the auto choice).
@@ -603,9 +584,10 @@ static int bin_mode(const DeviceState& d) {
 // Ray-binning scratch of a stream (mrt_bin.h) for batches of up to n rays.
 static constexpr size_t kBinHist = (size_t(1) << kBinBits) + 64;   // bins + the valid count, padded
 static int ensure_bin(StreamCtx& c, size_t n) {
-    return grow(c, {{(void**)&c.bin_keys, n * sizeof(uint16_t)}, {(void**)&c.bin_perm, 2 * n * sizeof(uint32_t)},
+    return reserve(c.own, &c.stream,
+                   {{(void**)&c.bin_keys, n * sizeof(uint16_t)}, {(void**)&c.bin_perm, 2 * n * sizeof(uint32_t)},
                     {(void**)&c.bin_hist, 2 * kBinHist * sizeof(uint32_t)}},
-                {{&c.bin_cap, n}});
+                   {{&c.bin_cap, n}});
 }
 
 // Binning of a ray batch o[i] / d[i], i < n (host bound), into permutation
@@ -634,7 +616,7 @@ static int bin_grid(const DeviceState& d, size_t n) {   // fewer blocks: fewer p
 }
 
 static int ensure_slots(StreamCtx& c, size_t slots) {
-    return grow(c, {{(void**)&c.hitbuf, slots * sizeof(float4)}}, {{&c.hit_slots, slots}});
+    return reserve(c.own, &c.stream, {{(void**)&c.hitbuf, slots * sizeof(float4)}}, {{&c.hit_slots, slots}});
 }
 
 // Resident workgroups per CU of one kernel instantiation (occupancy API, cached).
@@ -907,10 +889,12 @@ static int launch_chain(Scene& s, StreamCtx& c, const RenderParams& P0, bool cou
     // the same frame, at the fused kernel's speed for that chunk only.
     const int pi = std::min(P0.adapt_n, kEstPasses - 1);
     if (g_tune.chain_est && !c.est_dev) {
-        HIP_OK(hipMalloc((void**)&c.est_dev, kEstPasses * 64 * sizeof(uint32_t)));
+        int rc;
+        if ((rc = c.own.alloc(c.est_dev, kEstPasses * 64 * sizeof(uint32_t)))) return rc;
         HIP_OK(hipMemsetAsync(c.est_dev, 0, kEstPasses * 64 * sizeof(uint32_t), stream));
-        HIP_OK(hipHostMalloc((void**)&c.est_pinned, kEstPasses * 64 * sizeof(uint32_t)));
-        HIP_OK(hipEventCreateWithFlags(&c.est_ev, hipEventDisableTiming));
+        if ((rc = c.own.pinned(c.est_pinned, kEstPasses * 64 * sizeof(uint32_t))) ||
+            (rc = c.own.event(c.est_ev, hipEventDisableTiming)))
+            return rc;
         c.est.assign(kEstPasses * 64, 0u);
     }
     if (c.est_pending && hipEventQuery(c.est_ev) == hipSuccess) {   // the last copy has landed: no wait
@@ -973,7 +957,7 @@ static int launch_chain(Scene& s, StreamCtx& c, const RenderParams& P0, bool cou
     const size_t ctl = ctl_q + 256 + 64;
     const uint64_t n4 = 2 * entries + 2 * entries + entries + entries + 4 * spcap + (P0.adapt_n ? per : 0);
     const uint64_t bytes = n4 * 16 + entries * (uint64_t)W * 4 + entries * (uint64_t)split * 4 + ctl + spcap;
-    if ((rc = grow(c, {{&c.chain, (size_t)bytes}}, {{&c.chain_bytes, (size_t)bytes}}))) return rc;
+    if ((rc = reserve(c.own, &c.stream, {{&c.chain, (size_t)bytes}}, {{&c.chain_bytes, (size_t)bytes}}))) return rc;
     RenderParams Q = P0;
     float4* f4 = static_cast<float4*>(c.chain);
     Q.ch_ray = f4; f4 += 2 * entries;
@@ -1034,7 +1018,7 @@ static int launch_chain_adaptive(Scene& s, StreamCtx& c, RenderParams& P, bool c
     const uint64_t ucol_n = lanes * (uint64_t)maxs * (uint64_t)maxs;
     const uint64_t bytes = lanes * 16 + 2 * lanes * 4 + 256 + ucol_n * 16;
     int cur = 0, rc;
-    if ((rc = grow(c, {{&c.adapt, (size_t)bytes}}, {{&c.adapt_bytes, (size_t)bytes}}))) return rc;
+    if ((rc = reserve(c.own, &c.stream, {{&c.adapt, (size_t)bytes}}, {{&c.adapt_bytes, (size_t)bytes}}))) return rc;
     float4* res = static_cast<float4*>(c.adapt);
     float4* ucol = res + lanes;
     uint32_t* lists = reinterpret_cast<uint32_t*>(ucol + ucol_n);
@@ -1273,7 +1257,7 @@ using namespace mrt;
 // What the entries share:
 //   current_replica   the scene's current replica (device 0 before the first upload), made current
 //   ray_args_check    the argument checks of the caller-ray entries, before any device call
-//   Staged            the device copies of a synchronous entry's host arrays, freed when it returns
+//   Staged            the device copies of a synchronous entry's host arrays: a DevOwner, freed when it returns
 //   begin_query / end_launch (above launch_render)   the bracket of a launch that is not a render
 //   frame_params, seed_or_default, ensure_frame      one-camera frame setup
 // A synchronous entry is: checks, current_replica, stage in, its async body, copy out, its own
@@ -1301,14 +1285,12 @@ static int ray_args_check(const mrt_scene* s, size_t n, int32_t row_width, std::
 }
 
 // One allocation per array per call; after a failure (rc) every further call does nothing.
-struct Staged {
-    std::vector<void*> bufs;
+struct Staged : DevOwner {
     int rc = MRT_OK;
-    ~Staged() { for (void* p : bufs) (void)hipFree(p); }
     template <typename T> T* out(size_t bytes) {
-        void* p = nullptr;
-        if (rc == MRT_OK && (rc = alloc(p, bytes)) == MRT_OK) bufs.push_back(p);
-        return static_cast<T*>(p);
+        T* p = nullptr;
+        if (rc == MRT_OK) rc = alloc(p, bytes);
+        return p;
     }
     template <typename T> T* in(const T* host, size_t bytes) {   // a null host array stays null
         T* p = host ? out<T>(bytes) : nullptr;
@@ -1317,7 +1299,6 @@ struct Staged {
     }
     int back(void* host, const void* dev, size_t bytes) { return copy(host, dev, bytes, hipMemcpyDeviceToHost); }
 private:
-    static int alloc(void*& p, size_t bytes) { HIP_OK(hipMalloc(&p, bytes)); return MRT_OK; }
     static int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
         HIP_OK(hipMemcpy(dst, src, bytes, kind)); return MRT_OK;
     }
@@ -1336,17 +1317,9 @@ static int frame_params(const Scene& S, const mrt_camera* cam, const mrt_render_
     return MRT_OK;
 }
 
-// the replica's frame buffers of the synchronous renders hold px pixels; sync_stream: what may still read the old ones
-static int ensure_frame(DeviceState& d, size_t px, const hipStream_t* sync_stream) {
-    if (px <= d.frame_px) return MRT_OK;
-    if (sync_stream) HIP_OK(hipStreamSynchronize(*sync_stream));
-    if (d.d_rgb) (void)hipFree(d.d_rgb);
-    if (d.d_rgb8) (void)hipFree(d.d_rgb8);
-    d.d_rgb = nullptr; d.d_rgb8 = nullptr; d.frame_px = 0;
-    HIP_OK(hipMalloc((void**)&d.d_rgb, px * 12));
-    HIP_OK(hipMalloc((void**)&d.d_rgb8, px * 3));
-    d.frame_px = px;
-    return MRT_OK;
+// the replica's frame buffers of the synchronous renders hold px pixels; drain: what may still read the old ones
+static int ensure_frame(DeviceState& d, size_t px, const hipStream_t* drain) {
+    return reserve(d.own, drain, {{(void**)&d.d_rgb, px * 12}, {(void**)&d.d_rgb8, px * 3}}, {{&d.frame_px, px}});
 }
 
 extern "C" {
@@ -1534,13 +1507,8 @@ static mrt_hit to_hit(const Scene& S, const float4& v) {
 // is copied to the caller's host buffers once.  Each pixel is a pure function of
 // (scene, camera, pixel, seed), so the frame is bit-identical to a one-device
 // render.  Hit records (want_hits, debug / parity) still come back per share.
-static int ensure_buf(void*& p, size_t& cap, size_t bytes, hipStream_t sync_on) {
-    if (bytes <= cap) return MRT_OK;
-    if (p) { HIP_OK(hipStreamSynchronize(sync_on)); (void)hipFree(p); }
-    p = nullptr; cap = 0;
-    HIP_OK(hipMalloc(&p, bytes ? bytes : 16));
-    cap = bytes;
-    return MRT_OK;
+static int ensure_buf(DevOwner& own, void** p, size_t& cap, size_t bytes, hipStream_t drain) {
+    return reserve(own, &drain, {{p, bytes}}, {{&cap, bytes}});
 }
 static int render_shared(mrt_scene* s, const mrt_camera* cam, const mrt_render_opts* opts, float* rgb, uint8_t* rgb8,
                          mrt_hit* hits) {
@@ -1553,12 +1521,12 @@ static int render_shared(mrt_scene* s, const mrt_camera* cam, const mrt_render_o
     if ((rc = ensure_device(S, opts->device))) return rc;
     DeviceState& dc = *S.dev;
     HIP_OK(hipSetDevice(dc.device));
-    if (!dc.gather_stream) HIP_OK(hipStreamCreateWithFlags(&dc.gather_stream, hipStreamNonBlocking));
+    if (!dc.gather_stream && (rc = dc.own.stream(dc.gather_stream))) return rc;
     const hipStream_t gs = dc.gather_stream;
     const size_t px = (size_t)W * H;
     if ((rc = ensure_frame(dc, px, &gs)) ||
-        (rc = ensure_buf(reinterpret_cast<void*&>(dc.g_tiles), dc.g_tiles_cap, (size_t)bpf * tile_f * sizeof(float), gs)) ||
-        (rc = ensure_buf(reinterpret_cast<void*&>(dc.g_items), dc.g_items_cap, (size_t)bpf * sizeof(int32_t), gs)))
+        (rc = ensure_buf(dc.own, (void**)&dc.g_tiles, dc.g_tiles_cap, (size_t)bpf * tile_f * sizeof(float), gs)) ||
+        (rc = ensure_buf(dc.own, (void**)&dc.g_items, dc.g_items_cap, (size_t)bpf * sizeof(int32_t), gs)))
         return rc;
     struct Share {
         int device = -1;
@@ -1587,21 +1555,21 @@ static int render_shared(mrt_scene* s, const mrt_camera* cam, const mrt_render_o
         for (int j = 0; j < k; j++) slot += sh[j].device == q.device;
         if (hipSetDevice(q.device) != hipSuccess) { set_error("hipSetDevice"); rc = MRT_ERR_HIP; break; }
         while ((int)q.d->share_streams.size() <= slot) {
-            hipStream_t st;
-            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { set_error("stream"); rc = MRT_ERR_HIP; break; }
+            hipStream_t st = nullptr;
+            if (q.d->own.stream(st) != MRT_OK) { set_error("stream"); rc = MRT_ERR_HIP; break; }
             q.d->share_streams.push_back(st);
         }
         if (rc) break;
         while ((int)q.d->share_bufs.size() <= slot) q.d->share_bufs.push_back(new ShareBuf());
         q.stream = q.d->share_streams[slot];
         q.buf = q.d->share_bufs[slot];
-        if (!q.buf->done && hipEventCreateWithFlags(&q.buf->done, hipEventDisableTiming) != hipSuccess) {
+        if (!q.buf->done && q.d->own.event(q.buf->done, hipEventDisableTiming) != MRT_OK) {
             set_error("event"); rc = MRT_ERR_HIP; break;
         }
         if (q.ni == 0) continue;
         const size_t tb = q.ni * tile_f * sizeof(float);
-        if ((rc = ensure_buf(reinterpret_cast<void*&>(q.buf->items), q.buf->items_cap, q.ni * sizeof(int32_t), q.stream)) ||
-            (rc = ensure_buf(reinterpret_cast<void*&>(q.buf->tiles), q.buf->tiles_cap, tb, q.stream)))
+        if ((rc = ensure_buf(q.d->own, (void**)&q.buf->items, q.buf->items_cap, q.ni * sizeof(int32_t), q.stream)) ||
+            (rc = ensure_buf(q.d->own, (void**)&q.buf->tiles, q.buf->tiles_cap, tb, q.stream)))
             break;
         if (hipMemcpyAsync(q.buf->items, all.data() + q.first, q.ni * sizeof(int32_t), hipMemcpyHostToDevice, q.stream) !=
             hipSuccess) {
@@ -1852,11 +1820,9 @@ static int surface_groups(const Scene& S, DeviceState& d) {
         }
     };
     runs(S.obj_mesh, S.obj_tri);
-    for (const Blas& b : S.blas) runs(b.obj_mesh, b.obj_tri);   // the PrimShade order of upload_scene
-    SurfaceGroup* p = nullptr;
-    HIP_OK(hipMalloc((void**)&p, std::max<size_t>(1, G.size()) * sizeof(SurfaceGroup)));
-    d.bufs.push_back(p);
-    if (!G.empty()) HIP_OK(hipMemcpy(p, G.data(), G.size() * sizeof(SurfaceGroup), hipMemcpyHostToDevice));
+    for (const Blas& b : S.blas) runs(b.obj_mesh, b.obj_tri);   // the PrimShade order of build_image
+    SurfaceGroup* p = nullptr;   // (an empty table is 16 bytes, one record's size, as every empty upload)
+    if (const int rc = d.own.upload(p, G.data(), G.size() * sizeof(SurfaceGroup))) return rc;
     d.n_sgroups = (int)G.size();
     d.sgroups = p;
     return MRT_OK;

@@ -23,7 +23,6 @@ static constexpr int kWG = 256;          // threads per workgroup (4 waves)
 static constexpr int kLdsStack = 16;     // stack entries per lane kept in LDS (max seen: 11)
 static constexpr int kGlobalStack = 240; // spill entries per thread in HBM: 256 in all, the reference's stack (src/BVH.cpp:1133)
 static constexpr int kTableWords = 4096; // rcp[2048] + rsqrt[2048] (u16)
-static constexpr int kLdsNodes = 64;     // LN walks: the world hierarchy's first 64 nodes (breadth first) staged in LDS
 
 struct DRay {
     float o[3], d[3], id[3];
@@ -311,28 +310,7 @@ __device__ __forceinline__ int nearest_slot(int bits, const float (&tn)[4]) {
     return best;
 }
 
-// Device child word of a QNode slot: >= 0 inner node; kEmptySlot; otherwise
-// ~(leaf << 4 | check << 3 | proxy << 2 | (count - 1)) with count = objects in
-// the packet, proxy = the packet has ProxyObject (checkOut) lanes and check = it
-// has alpha-mapped or motion-blurred triangles (the host re-encodes the
-// canonical ~leaf on upload).
-__host__ __device__ __forceinline__ int32_t leaf_child(uint32_t leaf, int count, bool proxy = false, bool check = false) {
-    return ~(int32_t)((leaf << 4) | (check ? 8u : 0u) | (proxy ? 4u : 0u) | (uint32_t)(count - 1));
-}
-
-// QNode::pad[0] of a device node: its slot kinds, set on upload from the child
-// words (mrt_upload.hip, upload_scene): bits 0-3 inner child, 4-7 leaf packet,
-// 8-11 leaf packet with ProxyObject lanes.  One dword of the node's own line, read
-// instead of decoding the four child words in every step.
-__host__ __device__ __forceinline__ uint32_t slot_kinds(const int32_t child[4]) {
-    uint32_t k = 0;
-    for (int i = 0; i < 4; i++) {
-        const int32_t ch = child[i];
-        if (ch >= 0) k |= 1u << i;
-        else if (ch != kEmptySlot) k |= (1u << (4 + i)) | ((~(uint32_t)ch & 4u) ? 1u << (8 + i) : 0u);
-    }
-    return k;
-}
+// the slot kinds of a device node (QNode::pad[0]: slot_kinds, mrt_types.h)
 __device__ __forceinline__ int node_kinds(const float4* q) { return reinterpret_cast<const int32_t*>(q)[28]; }
 __device__ __forceinline__ int kinds_inner(int k) { return k & 15; }
 __device__ __forceinline__ int kinds_leaf(int k) { return (k >> 4) & 15; }

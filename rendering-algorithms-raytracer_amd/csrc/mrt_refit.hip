@@ -11,7 +11,7 @@
 // kernels over that BLAS's range, one kernel that recomputes the box of each of its instances
 // from the refitted root, then the world tree.  A motion-blurred world mesh: both vertex sets,
 // one kernel that recomputes the union box of each of its MBObject lanes, then the world tree.
-// One pipeline serves them all: a RefitTree (mrt_device.h) is the world or a BLAS, with one
+// One pipeline serves them all: a RefitTree (mrt_image.h) is the world or a BLAS, with one
 // height_schedule, enqueue_tree and read_tree for either; enqueue_mesh is the launch sequence
 // of every mesh entry, refit_replicas the per-replica loop of every synchronous entry and
 // async_ready what every async entry asks of the scene.
@@ -285,14 +285,6 @@ __global__ __launch_bounds__(kRefitWG) void refit_motion_box_kernel(float4* __re
     d_store_box(fixed, f, b);
 }
 
-template <typename T>
-int dev_array(DeviceState& d, T*& dst, const void* src, size_t bytes) {
-    HIP_OK(hipMalloc((void**)&dst, bytes ? bytes : 16));
-    d.bufs.push_back(dst);   // freed with the replica
-    if (bytes) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return MRT_OK;
-}
-
 // The height schedule of tree T (`what` in the messages) from its canonical nodes N and n_leaves
 // packets: T.off by height and, appended to `order`, the nodes sorted by height in device
 // numbers (perm[i]; perm empty: T.node_base + i).  Every child has a larger canonical number
@@ -363,11 +355,12 @@ int prepare(const Scene& s, DeviceState& d) {
             if (s.instances[i].blas == (int32_t)b) binsts.push_back((int32_t)i);
         R.n_inst = (uint32_t)binsts.size() - R.inst_at;
     }
-    if ((rc = dev_array(d, d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_array(d, d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4)))) return rc;
-    if ((rc = dev_array(d, d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_array(d, d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float)))) return rc;
-    if ((rc = dev_array(d, d.refit_blas_insts, binsts.data(), binsts.size() * sizeof(int32_t)))) return rc;
+    if ((rc = d.own.upload(d.refit_order, order.data(), order.size() * sizeof(int32_t))) ||
+        (rc = d.own.upload(d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4))) ||
+        (rc = d.own.upload(d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t))) ||
+        (rc = d.own.upload(d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float))) ||
+        (rc = d.own.upload(d.refit_blas_insts, binsts.data(), binsts.size() * sizeof(int32_t))))
+        return rc;
     d.world.order = d.refit_order;   // each tree's part of the one list
     const int32_t* at = d.refit_order + d.world.n_nodes;
     for (DeviceState::BlasRange& R : d.blas) {
@@ -378,10 +371,9 @@ int prepare(const Scene& s, DeviceState& d) {
     for (size_t o = s.obj_mesh.size(); o-- > 0;)
         if (s.obj_mesh[o] >= 0) d.mesh_prim0[(size_t)s.obj_mesh[o]] = (int32_t)o;
     // the packet boxes of the world and of every BLAS, by device packet number (the child words' own)
-    HIP_OK(hipMalloc((void**)&d.refit_lbox, std::max<size_t>(1, d.n_leaves_all) * 2 * sizeof(float4)));
-    d.bufs.push_back(d.refit_lbox);
-    HIP_OK(hipEventCreate(&d.refit_ev0));
-    HIP_OK(hipEventCreate(&d.refit_ev1));
+    if ((rc = d.own.alloc(d.refit_lbox, std::max<size_t>(1, d.n_leaves_all) * 2 * sizeof(float4))) ||
+        (rc = d.own.event(d.refit_ev0)) || (rc = d.own.event(d.refit_ev1)))
+        return rc;
     d.refit_ready = true;
     return MRT_OK;
 }
@@ -454,15 +446,9 @@ int enqueue_mesh(DeviceState& d, int m, int kind, int blas, const float* d_verts
     return enqueue_world(d, stream);
 }
 
-// the synchronous entries' staging buffer on replica d holds `need` floats
+// the synchronous entries' staging buffer on replica d holds `need` floats (they synchronise before they return: no drain)
 int stage_reserve(DeviceState& d, size_t need) {
-    if (need <= d.refit_stage_cap) return MRT_OK;
-    if (d.refit_stage) (void)hipFree(d.refit_stage);
-    d.refit_stage = nullptr;
-    d.refit_stage_cap = 0;
-    HIP_OK(hipMalloc((void**)&d.refit_stage, need * sizeof(float)));
-    d.refit_stage_cap = need;
-    return MRT_OK;
+    return reserve(d.own, nullptr, {{(void**)&d.refit_stage, need * sizeof(float)}}, {{&d.refit_stage_cap, need}});
 }
 
 // id joins a stale list (Scene::host_mesh_stale, host_blas_stale) once

@@ -2,13 +2,15 @@
 #pragma once
 #include <stdint.h>
 
+#include "mrt_math.h"   // MRT_HD: host and device under hipcc, a plain inline function otherwise
+
 namespace mrt {
 
 // 4-wide node, one 128-B line.  SoA boxes exactly as QBVH_Node
 // (reference src/BVH.h:83-109): minX[4] minY[4] minZ[4] maxX[4] maxY[4] maxZ[4].
 // child[i] >= 0: inner node index; child[i] == INT32_MIN: empty slot;
 // otherwise ~child[i] is a leaf-packet index.  The device copy keeps its slot kinds
-// in pad[0] (slot_kinds, mrt_kernels.h).
+// in pad[0] (slot_kinds, below).
 struct alignas(16) QNode {
     float box[24];
     int32_t child[4];
@@ -33,6 +35,30 @@ struct alignas(16) DLeaf {
 static_assert(sizeof(DLeaf) == 160, "DLeaf must be 160 B");
 
 static constexpr int32_t kEmptySlot = (int32_t)0x80000000u;
+static constexpr int kLdsNodes = 64;     // LN walks: the world hierarchy's first 64 nodes (breadth first) staged in LDS
+
+// Device child word of a QNode slot: >= 0 inner node; kEmptySlot; otherwise
+// ~(leaf << 4 | check << 3 | proxy << 2 | (count - 1)) with count = objects in
+// the packet, proxy = the packet has ProxyObject (checkOut) lanes and check = it
+// has alpha-mapped or motion-blurred triangles (the host re-encodes the
+// canonical ~leaf on upload).
+MRT_HD int32_t leaf_child(uint32_t leaf, int count, bool proxy = false, bool check = false) {
+    return ~(int32_t)((leaf << 4) | (check ? 8u : 0u) | (proxy ? 4u : 0u) | (uint32_t)(count - 1));
+}
+
+// QNode::pad[0] of a device node: its slot kinds, set in the device image from the child
+// words (host_image.cpp): bits 0-3 inner child, 4-7 leaf packet, 8-11 leaf packet with
+// ProxyObject lanes.  One dword of the node's own line, read instead of decoding the four
+// child words in every step.
+MRT_HD uint32_t slot_kinds(const int32_t child[4]) {
+    uint32_t k = 0;
+    for (int i = 0; i < 4; i++) {
+        const int32_t ch = child[i];
+        if (ch >= 0) k |= 1u << i;
+        else if (ch != kEmptySlot) k |= (1u << (4 + i)) | ((~(uint32_t)ch & 4u) ? 1u << (8 + i) : 0u);
+    }
+    return k;
+}
 
 // A ProxyObject on the device (src/ProxyObject.cpp:76-95, src/Ray.cpp:27-31).
 struct alignas(16) DevInstance {

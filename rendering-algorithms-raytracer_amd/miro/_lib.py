@@ -34,6 +34,7 @@ EXPORTS = [
     "mrt_hit_surfaces_async", "mrt_scene_update_mesh", "mrt_scene_update_mesh_async",
     "mrt_scene_update_instances", "mrt_scene_update_instances_async", "mrt_scene_instance_count",
     "mrt_scene_instance_info", "mrt_scene_deform_mesh", "mrt_scene_deform_mesh_async",
+    "mrt_debug_live_resources",
 ]
 
 
@@ -254,6 +255,9 @@ def load():
         L.mrt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if hasattr(L, "mrt_debug_libm"):   # (absent from round-4 builds loaded for A/B runs via MRT_LIB)
         L.mrt_debug_libm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    if hasattr(L, "mrt_debug_live_resources"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_debug_live_resources.argtypes = []
+        L.mrt_debug_live_resources.restype = C.c_int64
     L.mrt_rcp_nr.argtypes = [C.c_float]
     L.mrt_rcp_nr.restype = C.c_float
     L.mrt_rsqrt_nr.argtypes = [C.c_float]

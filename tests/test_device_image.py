@@ -1,0 +1,33 @@
+"""The host image of a device replica (build_image, csrc/host_image.cpp) without a GPU:
+tests/native/device_image.cpp, built with g++ against the plain C++ host sources, builds three
+scenes -- the Cornell box (fewer than 64 world nodes: no LDS renumbering), a world teapot plus a
+BLAS of a second teapot with two instances (renumbered), a motion-blurred teapot beside the
+box -- and checks what every kernel relies on: child words, leaf words against their packets,
+slot kinds, the node permutation and its breadth-first head, BLAS roots, PrimShade indices,
+the time-1 vertices, and the byte total.  tests/golden/device_image_bytes.json holds
+mrt_scene_info.device_bytes of the same three scenes, recorded from an upload by the commit
+before build_image existed."""
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "rendering-algorithms-raytracer_amd", "csrc")
+
+
+def test_device_image(tmp_path):
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "device_image")
+    srcs = [os.path.join(HERE, "native", "device_image.cpp")] + [os.path.join(CSRC, f) for f in (
+        "host_build.cpp", "host_texture.cpp", "host_image.cpp")]
+    # -ffp-contract=off: the build's arithmetic as the library compiles it (csrc/mrt_math.h)
+    subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I", CSRC, "-o", exe] + srcs + ["-lpthread"],
+                   check=True, capture_output=True)
+    want = json.load(open(os.path.join(HERE, "golden", "device_image_bytes.json")))
+    r = subprocess.run([exe, os.path.join(HERE, "golden", "models")] + [str(want[k]) for k in ("cornell", "instanced", "motion")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
