@@ -613,6 +613,42 @@ int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit
 int mrt_hit_surfaces_async(mrt_scene* s, const float* d_o, const float* d_d, const mrt_hit* d_hits, size_t n,
                            mrt_surface* d_out, void* stream);
 
+/* ---- sample the lights at caller points: Light::sampleLight (src/Light.h:35;
+ * src/PointLight.cpp:8-81, src/RectangleLight.cpp:42-136, src/DomeLight.cpp:80-160) for n
+ * caller points, every light of the scene in scene order -- what Material::shade asks of the
+ * lights, without a ray, a hit or a material.  from, normal: n*3 floats, used as given
+ * (nothing is normalised); rvec: n*3 floats, the reflection vector of the specular term, or
+ * NULL = the zero vector, which Lambert::shade passes; time: n floats or NULL (= 0), the
+ * shadow rays' time (where an MBObject's triangle is).  secondary is the isSecondary argument:
+ * with it set a dome light takes one sample.
+ * per_light (nullable): n * n_lights * 4 floats, for point i and light l {E.r, E.g, E.b,
+ * outSpec} at (i * n_lights + l) * 4.  e (nullable; e and per_light may not both be NULL):
+ * n*3 floats, the float sum of E over the lights, added in light order starting from 0 --
+ * what Lambert::shade accumulates with kd = 1 and ka = 0 (src/Lambert.cpp:42-50).  A scene
+ * without lights writes zeros.
+ * Point i draws from the RNG stream of "pixel" i, eye-ray sample 0, path 0, of `seed` (0 =
+ * the default seed), the draws numbered from the first draw of chain level 0 plus
+ * first_draw: 0 is where the light loop of Lambert::shade starts, 1 where that of
+ * Blinn::shade starts, after its roulette draw (src/Blinn.cpp:195).  The lights consume draws
+ * in order, as in a frame.  So on the points and normals mrt_hit_surfaces gives for a
+ * camera's rays, `e` is the float RGB mrt_shade_hits gives a white Lambert surface there (one
+ * path), bit for bit, with the same shadow_rays.
+ * Shadows are the frame's: alpha-mapped, motion-blurred and instanced occluders, and the
+ * transparency walk of a rectangle / dome light with transparent_shadows.  Inputs are not
+ * checked for finiteness.  Conventions of mrt_sample_rays: argument checks before any device
+ * call, n = 0 is MRT_OK, n at most 2^28, the scene's current device; the synchronous form
+ * copies in and out, the async form takes device pointers, enqueues on `stream` and never
+ * synchronises.  mrt_scene_last_stats: shadow_rays (every trace counts), kernel_ms,
+ * node_visits / leaf_visits with count_visits, primary_rays = 0; MRT_ERR_OVERFLOW as for
+ * mrt_sample_rays. */
+int mrt_sample_lights(mrt_scene* s, const float* from, const float* normal, const float* rvec,
+                      const float* time, size_t n, uint32_t seed, uint32_t first_draw,
+                      int32_t secondary, int32_t count_visits, float* e, float* per_light);
+int mrt_sample_lights_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                            const float* d_time, size_t n, uint32_t seed, uint32_t first_draw,
+                            int32_t secondary, int32_t count_visits, float* d_e, float* d_per_light,
+                            void* stream);
+
 /* Camera::eyeRayAdaptive(x, y, .5, .5, .5, .5) (src/Camera.cpp:116-174) for every pixel of
  * a width x height frame, on the host (no device is touched): the rays mrt_render traces
  * at 1 spp with this seed, index y*width + x, lens and getTimeSample time included.

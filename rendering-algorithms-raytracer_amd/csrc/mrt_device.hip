@@ -1872,6 +1872,78 @@ int mrt_hit_surfaces(mrt_scene* s, const float* o, const float* d, const mrt_hit
     return st.back(out, bs, n * sizeof(mrt_surface));   // no counters: the host check has refused every bad record
 }
 
+// ---- Light::sampleLight for caller points (mrt_sample_lights): light_points_kernel, mrt_lights.hip
+// on device arrays (checked by the caller, n > 0)
+static int sample_lights_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                               const float* d_time, size_t n, uint32_t seed, uint32_t first_draw, int32_t secondary,
+                               int32_t count_visits, float* d_e, float* d_per_light, hipStream_t stream) {
+    int rc;
+    Scene& S = s->impl;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(S, dp))) return rc;
+    DeviceState& d = *dp;
+    StreamCtx* c = nullptr;
+    if ((rc = begin_query(S, d, stream, kCtrBytes, false, c))) return rc;
+    RenderParams P{};
+    fill_params(S, P);
+    P.seed = seed_or_default(seed);
+    P.gstack = c->gstack;
+    P.ctr = c->ctr;
+    P.fast_box = fast_box(d);
+    P.cus = d.cus;
+    P.scalar_nodes = g_tune.scalar_nodes & (d.boxes_ordered ? 7 : 3);
+    P.near_first = g_tune.near_first > 0 ? 1 : 0;   // the fused kernels' setting
+    // the band counters of the shadow launch, cleared with the statistics
+    P.queue = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(c->ctr) + CTR_N * sizeof(unsigned long long)) + 24 * 32;
+    LightQuery Q{d_from, d_normal, d_rvec, d_time, d_e, d_per_light, (uint32_t)n, first_draw, secondary};
+    const LightFn f = pick_light_points(count_visits != 0, P.fast_box != 0, d.special, d.has_alpha || d.has_mb, d.transparent);
+    // a chunk per wave; a whole number of workgroups per XCD once there are 8
+    const size_t blocks = (n + kWG - 1) / kWG;
+    int g = (int)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)std::min(d.grid, d.cus * blocks_per_cu(reinterpret_cast<KernelFn>(f), 0))));
+    if (g > 8) g &= ~7;
+    void* args[] = {&P, &Q};
+    HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(f), dim3(g), dim3(kWG), args, 0, stream));
+    if ((rc = end_launch(d, *c, stream))) return rc;
+    S.last = mrt_stats{};
+    return MRT_OK;
+}
+
+static int sample_lights_check(const mrt_scene* s, const void* from, const void* normal, size_t n, const void* e,
+                               const void* per_light) {
+    if (const int rc = ray_args_check(s, n, 0, {from, normal}, "point / normal")) return rc;
+    if (n && !e && !per_light) { set_error("null output arrays: e and per_light"); return MRT_ERR_INVALID; }
+    return MRT_OK;
+}
+
+int mrt_sample_lights_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                            const float* d_time, size_t n, uint32_t seed, uint32_t first_draw, int32_t secondary,
+                            int32_t count_visits, float* d_e, float* d_per_light, void* stream) {
+    const int rc = sample_lights_check(s, d_from, d_normal, n, d_e, d_per_light);
+    if (rc || n == 0) return rc;
+    return sample_lights_async(s, d_from, d_normal, d_rvec, d_time, n, seed, first_draw, secondary, count_visits, d_e,
+                               d_per_light, (hipStream_t)stream);
+}
+
+int mrt_sample_lights(mrt_scene* s, const float* from, const float* normal, const float* rvec, const float* time, size_t n,
+                      uint32_t seed, uint32_t first_draw, int32_t secondary, int32_t count_visits, float* e,
+                      float* per_light) {
+    int rc = sample_lights_check(s, from, normal, n, e, per_light);
+    if (rc || n == 0) return rc;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(s->impl, dp))) return rc;
+    const size_t pl_bytes = n * s->impl.lights.size() * 16;
+    Staged st;
+    const float *bf = st.in(from, n * 12), *bn = st.in(normal, n * 12), *br = st.in(rvec, n * 12), *bt = st.in(time, n * 4);
+    float* be = e ? st.out<float>(n * 12) : nullptr;
+    float* bp = per_light ? st.out<float>(std::max<size_t>(pl_bytes, 16)) : nullptr;   // (a scene without lights: nothing is written)
+    if (st.rc) return st.rc;
+    if ((rc = sample_lights_async(s, bf, bn, br, bt, n, seed, first_draw, secondary, count_visits, be, bp, nullptr))) return rc;
+    if (e && (rc = st.back(e, be, n * 12))) return rc;
+    if (per_light && pl_bytes && (rc = st.back(per_light, bp, pl_bytes))) return rc;
+    mrt_stats tmp;
+    return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
+}
+
 int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32_t seed, float* o, float* d, float* time) {
     if (!cam || !o || !d || !time) { set_error("bad argument"); return MRT_ERR_INVALID; }
     CamParams C;

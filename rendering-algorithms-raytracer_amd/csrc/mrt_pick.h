@@ -12,6 +12,8 @@ namespace mrt {
 struct RenderParams;
 using KernelFn = void (*)(RenderParams);
 using ShadowFn = void (*)(RenderParams, size_t, int, int);
+struct LightQuery;
+using LightFn = void (*)(RenderParams, LightQuery);
 
 // Run-time bools to compile-time constants: with_bools(f, a, b) calls f(A, B) with
 // std::true_type / std::false_type values, so a generic lambda names the instantiation
@@ -65,5 +67,9 @@ KernelFn pick_adapt_combine();
 KernelFn pick_primary_rays(bool c, bool f, bool inst, bool check, bool xone);
 KernelFn pick_shade_rays(bool c, bool po, bool f, bool inst, int rec);
 KernelFn pick_shade_mode_rays(bool resolve, bool c, bool po, bool inst);
+// mrt_lights.hip: Light::sampleLight at caller points (mrt_sample_lights).  check: the special-leaf
+// scene has alpha-mapped or motion-blurred lanes; xp: a rectangle / dome light with transparent
+// shadows (the transparency walk, compiled into these variants only)
+LightFn pick_light_points(bool c, bool f, bool inst, bool check, bool xp);
 
 }  // namespace mrt

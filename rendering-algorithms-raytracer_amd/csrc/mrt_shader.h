@@ -215,6 +215,20 @@ struct RenderParams {
     uint32_t* ch_est;
 };
 
+// The arguments of light_points_kernel (mrt_lights.hip; mrt_sample_lights): n caller points,
+// device arrays.  Point i is "pixel" i of the RNG, sample 0, path 0.
+struct LightQuery {
+    const float* from;       // n * 3
+    const float* normal;     // n * 3, used as given
+    const float* rvec;       // n * 3 (nullable: the zero vector)
+    const float* time;       // n shadow-ray times (nullable: 0)
+    float* e;                // n * 3: the sum of E over the lights (nullable)
+    float* per_light;        // n * n_lights * 4: E.r, E.g, E.b, outSpec (nullable)
+    uint32_t n;
+    uint32_t first_draw;     // the first light's first draw is level_key(0) + first_draw
+    int32_t secondary;       // Light::sampleLight's isSecondary
+};
+
 // pow(spec, specExp) of Blinn::shade (src/Blinn.cpp:219-220): glibc's powf, which the
 // reference's float call resolves to, restated bit for bit (gl_powf, mrt_libm.h; round 6 --
 // round 5 evaluated it in double and rounded once, within 1 ulp of glibc's)
@@ -320,7 +334,9 @@ __device__ __forceinline__ v3 chain_combine(const RenderParams& P, const ChainRe
 
 // REC: 0 direct lighting only; 1 Blinn reflection / refraction chains; 2 also
 // path tracing (GI rays).  Compiled into the kernels that run such scenes only.
-template <bool POINT_ONLY, bool FAST, bool INST = false, int MODE = kFused, int REC = 0>
+// CHECK = false (light_points_kernel only): a special-leaf scene without alpha-mapped or
+// motion-blurred lanes, whose shadow walks leave those tests out (W_NOCHECK)
+template <bool POINT_ONLY, bool FAST, bool INST = false, int MODE = kFused, int REC = 0, bool CHECK = true>
 struct Shader {
     const RenderParams& P;
     const Trav& T;
@@ -357,7 +373,7 @@ struct Shader {
             DRay r = make_ray(from, L, shadow_time);
             DHit h{tMax, 0.f, 0.f, -1};
             constexpr uint32_t ANYHIT = W_ANY | walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) |
-                                        walk_opt(W_XONE, !INST);
+                                        walk_opt(W_XONE, !INST) | walk_opt(W_NOCHECK, !CHECK);
             return traverse<ANYHIT>(T, r, 0.001f, h, st);
         }
     }
@@ -381,7 +397,8 @@ struct Shader {
             shadow_rays++;
             const DRay r = make_ray(o, L, shadow_time);
             DHit h{tb, 0.f, 0.f, -1};
-            if (!traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST)>(T, r, 0.001f, h, st)) break;
+            if (!traverse<walk_opt(W_COUNT, COUNT) | walk_opt(W_FAST, FAST) | walk_opt(W_INST, INST) |
+                          walk_opt(W_NOCHECK, !CHECK)>(T, r, 0.001f, h, st)) break;
             int32_t ps_i = h.prim;
             if (INST && h.prim >= P.n_world) ps_i = inst_shade_index(h.prim, nullptr);
             const PrimShade ps = P.prims[ps_i];

@@ -1038,6 +1038,42 @@ class Scene:
         q.call("mrt_hit_surfaces", q.o, q.d, q.hits, q.n, _ptr(out))
         return out
 
+    # -- Light::sampleLight at caller points (src/Light.h:35)
+    def sampleLights(self, p, n, rvec=None, time=None, seed=0, first_draw=0, secondary=False, per_light=False,
+                     count_visits=False):
+        """What the scene's lights deliver at caller points (mrt_sample_lights): p, n (points
+        and normals, used as given) and rvec (the specular term's reflection vector; None: zero)
+        are (n, 3) or (H, W, 3); time (n,) / (H, W) or None (0) is the shadow rays' time.
+        Returns e, the sum of E over the lights in the points' shape -- Lambert::shade with kd =
+        1, ka = 0 -- or (e, per) with per_light, per (..., n_lights, 4) holding E.r, E.g, E.b,
+        outSpec of every light.  Point i draws from RNG stream i of `seed`, from draw
+        first_draw of chain level 0 (0: Lambert::shade's light loop, 1: Blinn::shade's);
+        secondary is isSecondary (a dome light takes one sample).  numpy arrays go through the
+        synchronous entry; contiguous float32 torch tensors on the scene's device through
+        mrt_sample_lights_async on the current stream."""
+        what = "sampleLights"
+        if rvec is not None:
+            if hasattr(rvec, "data_ptr") != hasattr(p, "data_ptr") or tuple(rvec.shape) != tuple(p.shape):
+                raise MRTError(f"{what}: rvec must be an array of the points' kind and shape")
+        q = _RayQuery(self, what, p, n, time)
+        if rvec is not None:
+            if q.tensors:
+                import torch
+                if not (rvec.is_cuda and rvec.dtype == torch.float32 and rvec.is_contiguous() and rvec.device.index == self.device):
+                    raise MRTError(f"{what}: tensors must be contiguous float32 on the scene's device")
+            else:
+                rvec = np.ascontiguousarray(rvec, np.float32)
+        shape = q.shape[:-1] + (len(self._lights), 4)
+        if q.tensors:
+            import torch
+            per = torch.empty(shape, dtype=torch.float32, device=p.device) if per_light else None
+        else:
+            per = np.zeros(shape, np.float32) if per_light else None
+        e = q.new()
+        q.call("mrt_sample_lights", q.o, q.d, _ptr(rvec), q.time, q.n, int(seed), int(first_draw), int(secondary),
+               int(count_visits), _ptr(e), _ptr(per), stats=True)
+        return (e, per) if per_light else e
+
     def primObject(self, prim: int):
         """HitInfo::obj / m_proxy of a hit id: (mesh id, triangle index, instance or -1)."""
         m, t, i = C.c_int32(), C.c_int32(), C.c_int32()
