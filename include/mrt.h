@@ -649,6 +649,58 @@ int mrt_sample_lights_async(mrt_scene* s, const float* d_from, const float* d_no
                             int32_t secondary, int32_t count_visits, float* d_e, float* d_per_light,
                             void* stream);
 
+/* ---- the samples behind mrt_sample_lights: what each light's loop took at each point, one
+ * record per sample, and the same query through wavefront passes (gen / bin / trace /
+ * resolve over the point list) instead of one fused kernel. */
+typedef struct {   /* one sample a light took at a point; 32 bytes */
+    float dir[3];  /* point -> light sample, as the light's loop holds it when it asks for the shadow answer */
+    float dist;    /* the distance the loop computed (point, rectangle); 1e12 for a dome sample */
+    float e[3];    /* what this sample adds to the light's sum at vis = 1 */
+    float vis;     /* the shadow answer: 1 visible, 0 occluded or rejected */
+} mrt_light_sample;
+
+/* The most samples each light can take at a point (a built scene; no device is touched):
+ * per_light[l] (nullable, n_lights entries) = 1 for a point light, max(1, samples) for a
+ * rectangle light and for a dome light, 1 for a dome light with `secondary` set; *total
+ * (nullable) = their sum M, the row stride of mrt_light_samples' records. */
+int mrt_scene_light_sample_cap(const mrt_scene* s, int32_t secondary, int32_t* per_light, int32_t* total);
+
+/* mrt_sample_lights with per-sample records.  from, normal, rvec, time, n, seed, first_draw,
+ * secondary, count_visits, e and per_light are mrt_sample_lights' (the same RNG stream per
+ * point, the same draw numbering, the same bits in e and per_light); e and per_light may both
+ * be NULL here, but at least one of samples, counts, e, per_light is required.
+ * counts (nullable): n * n_lights int32, the samples light l took at point i (the loop's
+ * `done`): 0 for a point light facing away, and for a dome call whose every draw was rejected.
+ * samples (nullable): n * M records, M from mrt_scene_light_sample_cap.  Point i's samples
+ * start at row i * M, in light order, then sample order, compact; rows past the sum of the
+ * point's counts are not written.
+ *   point light      dir = the normalised L, dist = distance, e = A * nDotL in all three
+ *                    channels; with cast_shadows 0, vis = 1 and no ray
+ *   rectangle light  dir = the normalised rd, dist = dist, e = E in all three channels (no
+ *                    cosine: the reference's rectangle light has none).  A sample whose nDotL
+ *                    is at most 0.001 is still a sample (the loop counts it): vis = 0, dist = 0,
+ *                    dir = rd as it stands (not normalised), e = the loop's E (stale falloff)
+ *   dome light       dir = dir, dist = 1e12, e = m_Gain * image / pdf; a rejected
+ *                    below-horizon draw is no sample (it consumes its two draws)
+ * A light's {E, outSpec} is the loop's own sum over its records: acc += e * vis in order,
+ * times 1 / count (a point light: e * vis).
+ * Refused (MRT_ERR_INVALID, before any device call): a scene with a transparent_shadows
+ * light (the wavefront shadow answer is one bit), M above 64, n * M at or above 2^32.
+ * Otherwise the conventions and statistics of mrt_sample_lights: shadow_rays counts the
+ * traces, kernel_ms, node_visits / leaf_visits with count_visits, primary_rays = 0,
+ * MRT_ERR_OVERFLOW.  A scene without lights (M = 0) writes zeros to e and nothing else.
+ * Inputs are not checked for finiteness; with finite inputs and light parameters every
+ * output is deterministic and independent of the tuning's schedules. */
+int mrt_light_samples(mrt_scene* s, const float* from, const float* normal, const float* rvec,
+                      const float* time, size_t n, uint32_t seed, uint32_t first_draw,
+                      int32_t secondary, int32_t count_visits,
+                      mrt_light_sample* samples, int32_t* counts, float* e, float* per_light);
+int mrt_light_samples_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                            const float* d_time, size_t n, uint32_t seed, uint32_t first_draw,
+                            int32_t secondary, int32_t count_visits,
+                            mrt_light_sample* d_samples, int32_t* d_counts, float* d_e, float* d_per_light,
+                            void* stream);
+
 /* Camera::eyeRayAdaptive(x, y, .5, .5, .5, .5) (src/Camera.cpp:116-174) for every pixel of
  * a width x height frame, on the host (no device is touched): the rays mrt_render traces
  * at 1 spp with this seed, index y*width + x, lens and getTimeSample time included.

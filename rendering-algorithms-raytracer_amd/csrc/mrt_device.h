@@ -196,6 +196,11 @@ struct StreamCtx {
     float4* ray_e = nullptr;                 // dome-light replay (RenderParams::ray_e / lrec)
     uint32_t* lrec = nullptr;
     size_t ray_e_cap = 0, lrec_cap = 0;
+    float* ls_aux = nullptr;                 // mrt_light_samples: per sample row, its factor of the specular sum
+    int32_t* ls_counts = nullptr;            //   per (point, light): samples taken, where the caller asks for none
+    size_t ls_aux_cap = 0, ls_counts_cap = 0;
+    void* ls_rec = nullptr;                  //   the records (mrt_light_sample), where the caller asks for none
+    size_t ls_rec_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr;
 };
 static constexpr int kMaxStreamCtx = 16;

@@ -1944,6 +1944,180 @@ int mrt_sample_lights(mrt_scene* s, const float* from, const float* normal, cons
     return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
 }
 
+// ---- mrt_light_samples: the same query through the frame's wavefront shadow passes over the
+// point list -- gen (light_gen_kernel), bin, trace (shadow_kernel), resolve (light_resolve_kernel)
+static int light_sample_cap(const Scene& S, bool secondary, int32_t* per_light) {
+    int64_t total = 0;
+    for (size_t l = 0; l < S.lights.size(); l++) {
+        const DevLight& L = S.lights[l];
+        const int32_t cap = L.type == MRT_POINT_LIGHT || (L.type == MRT_DOME_LIGHT && secondary) ? 1 : std::max(1, L.samples);
+        if (per_light) per_light[l] = cap;
+        total += cap;
+    }
+    return (int)std::min<int64_t>(total, INT32_MAX);
+}
+
+int mrt_scene_light_sample_cap(const mrt_scene* s, int32_t secondary, int32_t* per_light, int32_t* total) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    const int m = light_sample_cap(s->impl, secondary != 0, per_light);
+    if (total) *total = m;
+    return MRT_OK;
+}
+
+// scratch of a stream for n * m sample rows and n * n_lights counts; the records' own group
+static int ensure_light_samples(StreamCtx& c, size_t rows, size_t counts, bool records) {
+    if (const int rc = reserve(c.own, &c.stream, {{(void**)&c.ls_aux, rows * sizeof(float)}, {(void**)&c.ls_counts, counts * sizeof(int32_t)}},
+                               {{&c.ls_aux_cap, rows}, {&c.ls_counts_cap, counts}}))
+        return rc;
+    if (!records) return MRT_OK;
+    return reserve(c.own, &c.stream, {{&c.ls_rec, rows * sizeof(mrt_light_sample)}}, {{&c.ls_rec_cap, rows}});
+}
+
+// on device arrays (checked by the caller, n > 0)
+static int light_samples_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                               const float* d_time, size_t n, uint32_t seed, uint32_t first_draw, int32_t secondary,
+                               int32_t count_visits, mrt_light_sample* d_samples, int32_t* d_counts, float* d_e,
+                               float* d_per_light, hipStream_t stream) {
+    int rc;
+    Scene& S = s->impl;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(S, dp))) return rc;
+    DeviceState& d = *dp;
+    StreamCtx* cp = nullptr;
+    if ((rc = begin_query(S, d, stream, kCtrBytes, false, cp))) return rc;
+    StreamCtx& c = *cp;
+    const int m = light_sample_cap(S, secondary != 0, nullptr);
+    if (m == 0) {   // no lights: a zero sum, nothing else
+        if (d_e) HIP_OK(hipMemsetAsync(d_e, 0, n * 12, stream));
+    } else {
+        const size_t n_rays = n * (size_t)m, n_lights = S.lights.size();
+        const bool count = count_visits != 0;
+        if ((rc = ensure_rays(c, n, (size_t)m))) return rc;
+        if ((rc = ensure_light_samples(c, n_rays, n * n_lights, d_samples == nullptr))) return rc;
+        RenderParams P{};
+        fill_params(S, P);
+        P.seed = seed_or_default(seed);
+        P.gstack = c.gstack;
+        P.ctr = c.ctr;
+        P.fast_box = fast_box(d);
+        P.cus = d.cus;
+        P.scalar_nodes = g_tune.scalar_nodes & (d.boxes_ordered ? 7 : 3);
+        P.ray_o = c.rays;
+        P.ray_d = c.rays + n_rays;
+        P.occl = c.occl;
+        P.nrays = c.nrays;
+        P.max_shadow = m;
+        LightSamples G{};
+        G.q = LightQuery{d_from, d_normal, d_rvec, d_time, d_e, d_per_light, (uint32_t)n, first_draw, secondary};
+        G.rec = d_samples ? d_samples : static_cast<mrt_light_sample*>(c.ls_rec);
+        G.aux = c.ls_aux;
+        G.counts = d_counts ? d_counts : c.ls_counts;
+        G.m = m;
+        G.write_vis = d_samples ? 1 : 0;
+        const int blocks = (int)((n + kWG - 1) / kWG);   // n <= 2^28
+        void* pass_args[] = {&P, &G};
+        HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(pick_light_gen()), dim3(blocks), dim3(kWG), pass_args, 0, stream));
+        // the frame's shadow launch (launch_render): schedule, grid, walk order, bins
+        const bool inst = d.special, chk = d.has_alpha || d.has_mb, fb = P.fast_box != 0;
+        bool dome = false;
+        for (const DevLight& l : S.lights) dome |= l.type == MRT_DOME_LIGHT;
+        int sched = g_tune.shadow_sched >= 0 ? g_tune.shadow_sched : (dome ? 2 : 1), refill = kRefillMin;
+        ShadowFn sf = pick_shadow(count, fb, inst, sched == 2, chk);
+        int g = std::max(1, std::min(d.grid, d.cus * blocks_per_cu(reinterpret_cast<KernelFn>(sf), 0)));
+        if (sched && (g & 7)) g &= ~7;
+        if (g < 8) {
+            sched = 0;
+            sf = pick_shadow(count, fb, inst, false, chk);
+        }
+        P.near_first = g_tune.near_first >= 0 ? g_tune.near_first : (sched == 2 || inst ? 0 : 1);
+        if (bin_mode(d) & 1) {   // (no instance-major keys: a point list has no primary hits)
+            if ((rc = ensure_bin(c, n_rays))) return rc;
+            BinArgs A = bin_args(d, c, 0, P.ray_o, P.ray_d, n_rays);
+            A.nrays = P.nrays;
+            A.m = (uint32_t)m;
+            if ((rc = bin_rays(A, bin_grid(d, n_rays), stream))) return rc;
+            P.sh_perm = A.perm;
+            P.sh_perm_n = bin_total(A);
+        }
+        // the band counters of the shadow launch, cleared with the statistics
+        P.queue = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(c.ctr) + CTR_N * sizeof(unsigned long long)) + 24 * 32;
+        size_t nr = n_rays;
+        void* args[] = {&P, &nr, &sched, &refill};
+        HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(sf), dim3(g), dim3(kWG), args, 0, stream));
+        P.sh_perm = nullptr;
+        P.sh_perm_n = nullptr;
+        if (d_samples || d_e || d_per_light)   // (counts alone: nothing is left to write)
+            HIP_OK(hipLaunchKernel(reinterpret_cast<const void*>(pick_light_resolve()), dim3(blocks), dim3(kWG), pass_args, 0, stream));
+    }
+    if ((rc = end_launch(d, c, stream))) return rc;
+    S.last = mrt_stats{};
+    return MRT_OK;
+}
+
+// every refusal, before any device call
+static int light_samples_check(const mrt_scene* s, const void* from, const void* normal, size_t n, const void* samples,
+                               const void* counts, const void* e, const void* per_light, int32_t secondary) {
+    if (const int rc = ray_args_check(s, n, 0, {from, normal}, "point / normal")) return rc;
+    if (n && !samples && !counts && !e && !per_light) {
+        set_error("null output arrays: samples, counts, e and per_light");
+        return MRT_ERR_INVALID;
+    }
+    for (const DevLight& l : s->impl.lights)
+        if (l.transparent) {
+            set_error("a light with transparent shadows: the wavefront shadow answer is one bit (use mrt_sample_lights)");
+            return MRT_ERR_INVALID;
+        }
+    const int m = light_sample_cap(s->impl, secondary != 0, nullptr);
+    if (m > kMaxWaveShadow) {
+        set_error("more than 64 light samples per point (mrt_scene_light_sample_cap)");
+        return MRT_ERR_INVALID;
+    }
+    if ((uint64_t)n * (uint64_t)m >= (uint64_t(1) << 32)) {
+        set_error("too many light-sample rows: n * M reaches 2^32");
+        return MRT_ERR_INVALID;
+    }
+    return MRT_OK;
+}
+
+int mrt_light_samples_async(mrt_scene* s, const float* d_from, const float* d_normal, const float* d_rvec,
+                            const float* d_time, size_t n, uint32_t seed, uint32_t first_draw, int32_t secondary,
+                            int32_t count_visits, mrt_light_sample* d_samples, int32_t* d_counts, float* d_e,
+                            float* d_per_light, void* stream) {
+    const int rc = light_samples_check(s, d_from, d_normal, n, d_samples, d_counts, d_e, d_per_light, secondary);
+    if (rc || n == 0) return rc;
+    return light_samples_async(s, d_from, d_normal, d_rvec, d_time, n, seed, first_draw, secondary, count_visits, d_samples,
+                               d_counts, d_e, d_per_light, (hipStream_t)stream);
+}
+
+int mrt_light_samples(mrt_scene* s, const float* from, const float* normal, const float* rvec, const float* time, size_t n,
+                      uint32_t seed, uint32_t first_draw, int32_t secondary, int32_t count_visits, mrt_light_sample* samples,
+                      int32_t* counts, float* e, float* per_light) {
+    int rc = light_samples_check(s, from, normal, n, samples, counts, e, per_light, secondary);
+    if (rc || n == 0) return rc;
+    DeviceState* dp = nullptr;
+    if ((rc = current_replica(s->impl, dp))) return rc;
+    const size_t n_lights = s->impl.lights.size();
+    const size_t rec_bytes = n * (size_t)light_sample_cap(s->impl, secondary != 0, nullptr) * sizeof(mrt_light_sample);
+    const size_t cnt_bytes = n * n_lights * 4, pl_bytes = n * n_lights * 16;
+    Staged st;
+    const float *bf = st.in(from, n * 12), *bn = st.in(normal, n * 12), *br = st.in(rvec, n * 12), *bt = st.in(time, n * 4);
+    // the records go in as well: the rows past a point's count keep what the caller put there
+    mrt_light_sample* bs = samples && rec_bytes ? st.in(samples, rec_bytes) : nullptr;
+    int32_t* bc = counts ? st.out<int32_t>(std::max<size_t>(cnt_bytes, 16)) : nullptr;
+    float* be = e ? st.out<float>(n * 12) : nullptr;
+    float* bp = per_light ? st.out<float>(std::max<size_t>(pl_bytes, 16)) : nullptr;
+    if (st.rc) return st.rc;
+    if ((rc = light_samples_async(s, bf, bn, br, bt, n, seed, first_draw, secondary, count_visits, bs, bc, be, bp, nullptr)))
+        return rc;
+    if (samples && rec_bytes && (rc = st.back(samples, bs, rec_bytes))) return rc;
+    if (counts && cnt_bytes && (rc = st.back(counts, bc, cnt_bytes))) return rc;
+    if (e && (rc = st.back(e, be, n * 12))) return rc;
+    if (per_light && pl_bytes && (rc = st.back(per_light, bp, pl_bytes))) return rc;
+    mrt_stats tmp;
+    return mrt_scene_last_stats(s, &tmp);   // the counters; MRT_ERR_OVERFLOW
+}
+
 int mrt_camera_rays(const mrt_camera* cam, int32_t width, int32_t height, uint32_t seed, float* o, float* d, float* time) {
     if (!cam || !o || !d || !time) { set_error("bad argument"); return MRT_ERR_INVALID; }
     CamParams C;

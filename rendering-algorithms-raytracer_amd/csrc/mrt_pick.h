@@ -14,6 +14,8 @@ using KernelFn = void (*)(RenderParams);
 using ShadowFn = void (*)(RenderParams, size_t, int, int);
 struct LightQuery;
 using LightFn = void (*)(RenderParams, LightQuery);
+struct LightSamples;
+using LightPassFn = void (*)(RenderParams, LightSamples);
 
 // Run-time bools to compile-time constants: with_bools(f, a, b) calls f(A, B) with
 // std::true_type / std::false_type values, so a generic lambda names the instantiation
@@ -71,5 +73,9 @@ KernelFn pick_shade_mode_rays(bool resolve, bool c, bool po, bool inst);
 // scene has alpha-mapped or motion-blurred lanes; xp: a rectangle / dome light with transparent
 // shadows (the transparency walk, compiled into these variants only)
 LightFn pick_light_points(bool c, bool f, bool inst, bool check, bool xp);
+// mrt_lights.hip: the gen and resolve passes of mrt_light_samples (one lane per point, no
+// traversal: one instantiation each; the trace between them is pick_shadow's)
+LightPassFn pick_light_gen();
+LightPassFn pick_light_resolve();
 
 }  // namespace mrt

@@ -229,6 +229,19 @@ struct LightQuery {
     int32_t secondary;       // Light::sampleLight's isSecondary
 };
 
+// The arguments of light_gen_kernel / light_resolve_kernel (mrt_lights.hip; mrt_light_samples):
+// the same points through wavefront passes.  Point i's sample rows are [i * m, i * m + sum of
+// its counts), its rays P.ray_o / P.ray_d [i * m, i * m + P.nrays[i]) in sample order.
+static constexpr float kVisPending = 2.0f;   // mrt_light_sample::vis between gen and resolve: a ray was written
+struct LightSamples {
+    LightQuery q;            // the points and the outputs e / per_light (both nullable here)
+    mrt_light_sample* rec;   // n * m records: the caller's `samples`, or scratch
+    float* aux;              // n * m: a rectangle / dome sample's factor of the specular sum
+    int32_t* counts;         // n * n_lights: samples taken (the caller's `counts`, or scratch)
+    int32_t m;               // rows per point: mrt_scene_light_sample_cap's total
+    int32_t write_vis;       // resolve: rec is the caller's, store the answers into it
+};
+
 // pow(spec, specExp) of Blinn::shade (src/Blinn.cpp:219-220): glibc's powf, which the
 // reference's float call resolves to, restated bit for bit (gl_powf, mrt_libm.h; round 6 --
 // round 5 evaluated it in double and rounded once, within 1 ulp of glibc's)

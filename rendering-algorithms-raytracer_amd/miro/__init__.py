@@ -412,6 +412,8 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("a", "<f4"), ("b", "<f4"), ("prim", "<i4"),
 SURFACE_DTYPE = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("geo_n", "<f4", 3), ("tan", "<f4", 3), ("bitan", "<f4", 3),
                           ("u", "<f4"), ("v", "<f4"), ("material", "<i4"), ("mesh", "<i4"), ("tri", "<i4"),
                           ("inst", "<i4")])
+# mrt_light_sample (Scene.lightSamples): one sample a light took at a point
+LIGHT_SAMPLE_DTYPE = np.dtype([("dir", "<f4", 3), ("dist", "<f4"), ("e", "<f4", 3), ("vis", "<f4")])
 
 
 def makeMeshObjs(scene: "Scene", mesh: TriangleMesh, material):
@@ -1039,6 +1041,87 @@ class Scene:
         return out
 
     # -- Light::sampleLight at caller points (src/Light.h:35)
+    def _light_query(self, what, p, n, rvec, time):
+        """The checked inputs of sampleLights / lightSamples: the _RayQuery of (p, n, time) and
+        rvec as an array of the points' kind and shape (None stays None)."""
+        if rvec is not None:
+            if hasattr(rvec, "data_ptr") != hasattr(p, "data_ptr") or tuple(rvec.shape) != tuple(p.shape):
+                raise MRTError(f"{what}: rvec must be an array of the points' kind and shape")
+        q = _RayQuery(self, what, p, n, time)
+        if rvec is not None:
+            if q.tensors:
+                import torch
+                if not (rvec.is_cuda and rvec.dtype == torch.float32 and rvec.is_contiguous() and rvec.device.index == self.device):
+                    raise MRTError(f"{what}: tensors must be contiguous float32 on the scene's device")
+            else:
+                rvec = np.ascontiguousarray(rvec, np.float32)
+        return q, rvec
+
+    def lightSampleCap(self, secondary=False):
+        """(per_light, total) of mrt_scene_light_sample_cap: the most samples each light can take
+        at a point -- 1 for a point light, max(1, samples) for a rectangle or dome light, 1 for
+        a dome light with `secondary` -- as an int32 array, and their sum M.  No device call."""
+        per = np.zeros(len(self._lights), np.int32)
+        total = C.c_int32()
+        check(lib().mrt_scene_light_sample_cap(self.handle, int(bool(secondary)), per.ctypes.data, C.byref(total)),
+              "lightSampleCap")
+        return per, total.value
+
+    def lightSamples(self, p, n, rvec=None, time=None, seed=0, first_draw=0, secondary=False, samples=True, counts=True,
+                     e=False, per_light=False, count_visits=False):
+        """sampleLights with the per-sample records (mrt_light_samples): the same points, draws
+        and bits, through wavefront passes (gen / bin / trace / resolve).  Returns a dict of the
+        outputs asked for (at least one): "samples", per point M = lightSampleCap()[1] rows of
+        LIGHT_SAMPLE_DTYPE (dir, dist, e, vis), in light order then sample order, compact -- rows
+        past the sum of the point's counts are zero here, or keep what they held when `samples`
+        is the caller's own array of that shape, which is then written in place; "counts"
+        (..., n_lights) int32, the samples each light took; "e" and "per_light" as sampleLights
+        returns them.  For device tensors "samples" is (n, M, 8) float32 and "counts" (n,
+        n_lights) int32, on the current stream (mrt_light_samples_async).  A scene with a
+        transparent-shadow light, or with M above 64, is refused."""
+        what = "lightSamples"
+        own = not isinstance(samples, (bool, np.bool_))   # the caller's array, written in place
+        if not (own or samples or counts or e or per_light):
+            raise MRTError(f"{what}: at least one of samples, counts, e, per_light")
+        shape, count, tensors = self._pairs(what, p, n, time, None)
+        nl, m = len(self._lights), self.lightSampleCap(secondary)[1]
+        lead = shape[:-1]
+        if own:   # (checked before the scene goes to its device)
+            if tensors:
+                import torch
+                ok = (hasattr(samples, "data_ptr") and samples.is_cuda and samples.dtype == torch.float32 and
+                      samples.is_contiguous() and samples.device == p.device and tuple(samples.shape) == (count, m, 8))
+                want = f"a contiguous float32 ({count}, {m}, 8) tensor on the points' device"
+            else:
+                ok = (isinstance(samples, np.ndarray) and samples.dtype == LIGHT_SAMPLE_DTYPE and
+                      samples.flags.c_contiguous and samples.shape == lead + (m,))
+                want = f"a C-contiguous LIGHT_SAMPLE_DTYPE array of shape {lead + (m,)}"
+            if not ok:
+                raise MRTError(f"{what}: samples must be {want}")
+        q, rvec = self._light_query(what, p, n, rvec, time)
+        out = {}
+        if tensors:
+            import torch
+
+            def new(shape, dtype=torch.float32):
+                return torch.zeros(shape, dtype=dtype, device=p.device)
+            rec_shape, rec_type, cnt_shape, i32 = (count, m, 8), torch.float32, (count, nl), torch.int32
+        else:
+            def new(shape, dtype=np.float32):
+                return np.zeros(shape, dtype)
+            rec_shape, rec_type, cnt_shape, i32 = lead + (m,), LIGHT_SAMPLE_DTYPE, lead + (nl,), np.int32
+        if own or samples:
+            out["samples"] = samples if own else new(rec_shape, rec_type)
+        if counts:
+            out["counts"] = new(cnt_shape, i32)
+        if e:
+            out["e"] = new(q.shape)
+        if per_light:
+            out["per_light"] = new(lead + (nl, 4))
+        q.call("mrt_light_samples", q.o, q.d, _ptr(rvec), q.time, q.n, int(seed), int(first_draw), int(secondary),
+               int(count_visits), *(_ptr(out.get(k)) for k in ("samples", "counts", "e", "per_light")), stats=True)
+        return out
+
     def sampleLights(self, p, n, rvec=None, time=None, seed=0, first_draw=0, secondary=False, per_light=False,
                      count_visits=False):
         """What the scene's lights deliver at caller points (mrt_sample_lights): p, n (points
@@ -1051,18 +1134,7 @@ class Scene:
         secondary is isSecondary (a dome light takes one sample).  numpy arrays go through the
         synchronous entry; contiguous float32 torch tensors on the scene's device through
         mrt_sample_lights_async on the current stream."""
-        what = "sampleLights"
-        if rvec is not None:
-            if hasattr(rvec, "data_ptr") != hasattr(p, "data_ptr") or tuple(rvec.shape) != tuple(p.shape):
-                raise MRTError(f"{what}: rvec must be an array of the points' kind and shape")
-        q = _RayQuery(self, what, p, n, time)
-        if rvec is not None:
-            if q.tensors:
-                import torch
-                if not (rvec.is_cuda and rvec.dtype == torch.float32 and rvec.is_contiguous() and rvec.device.index == self.device):
-                    raise MRTError(f"{what}: tensors must be contiguous float32 on the scene's device")
-            else:
-                rvec = np.ascontiguousarray(rvec, np.float32)
+        q, rvec = self._light_query("sampleLights", p, n, rvec, time)
         shape = q.shape[:-1] + (len(self._lights), 4)
         if q.tensors:
             import torch

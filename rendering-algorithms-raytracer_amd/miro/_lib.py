@@ -35,6 +35,7 @@ EXPORTS = [
     "mrt_scene_update_instances", "mrt_scene_update_instances_async", "mrt_scene_instance_count",
     "mrt_scene_instance_info", "mrt_scene_deform_mesh", "mrt_scene_deform_mesh_async",
     "mrt_debug_live_resources", "mrt_sample_lights", "mrt_sample_lights_async",
+    "mrt_scene_light_sample_cap", "mrt_light_samples", "mrt_light_samples_async",
 ]
 
 
@@ -219,6 +220,12 @@ def load():
         L.mrt_sample_lights.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, vp, vp]
         L.mrt_sample_lights_async.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
                                               vp, vp, vp]
+    if hasattr(L, "mrt_light_samples"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        vp = C.c_void_p
+        L.mrt_scene_light_sample_cap.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int32)]
+        L.mrt_light_samples.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                        vp, vp, vp, vp]
+        L.mrt_light_samples_async.argtypes = L.mrt_light_samples.argtypes + [vp]
     if hasattr(L, "mrt_scene_update_mesh"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
         L.mrt_scene_update_mesh.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.mrt_scene_update_mesh_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
