@@ -463,6 +463,56 @@ int mrt_scene_deform_mesh(mrt_scene* s, int mesh, const float* verts, const floa
 int mrt_scene_deform_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_verts2,
                                 const float* d_normals, void* stream);
 
+/* ---- relighting in place: lights, a material's base record and the texels of a texture
+ * change on the replicas without a re-upload (the setters above mark the scene for one).
+ * Conventions of mrt_scene_update_mesh / _async: every argument is checked, with its own
+ * text in mrt_last_error, before any device call and before any change; the synchronous
+ * forms update every uploaded replica (they wait for the device first); the async forms
+ * need the scene uploaded to exactly one device, enqueue on `stream` and never synchronise
+ * (the first texture update of a replica allocates its scratch); a scene that is not
+ * uploaded (or due for a re-upload) is updated on the host; ordering against launches in
+ * flight on other streams is the caller's.
+ *
+ * mrt_scene_update_lights: Light::setPosition / setVertices / setPower / setSamples /
+ * setNoiseThreshold / setCastShadows (src/Light.h:20-29, src/PointLight.h, src/RectangleLight.h,
+ * src/DomeLight.h:52) on the lights that exist.  lights[n] replaces the parameters of the
+ * scene's n lights, converted as mrt_scene_add_light converts them; n must be the scene's
+ * light count, and every light keeps its type, its texture (dome) and its
+ * transparent_shadows (MRT_ERR_INVALID names the light and the field).  Both forms take a
+ * host pointer: the records travel as a kernel argument, so the update is stream-ordered. */
+int mrt_scene_update_lights(mrt_scene* s, const mrt_light* lights, int32_t n);
+int mrt_scene_update_lights_async(mrt_scene* s, const mrt_light* lights, int32_t n, void* stream);
+/* Lambert::setKd / setKa, Blinn::setKd / setKa / setKs / setSpecExp / setSpecAmt /
+ * setLightEmittedColor / setLightEmittedIntensity (src/Lambert.h:15-16, src/Blinn.h:30-45) on
+ * an existing material: the mrt_material fields (what mrt_scene_add_material set) and the
+ * derived emitter flag; the type must not change.  Optics, maps, environment map, gloss,
+ * translucency and dispersion stay as their setters left them. */
+int mrt_scene_update_material(mrt_scene* s, int material, const mrt_material* m);
+int mrt_scene_update_material_async(mrt_scene* s, int material, const mrt_material* m, void* stream);
+/* RawImage texels replaced (src/RawImage.h:21 m_rawData), same width, height and type:
+ * W*H*channels floats.  Environment maps and material maps read the new texels where the old
+ * ones were.  For every dome light of this texture DomeLight::setTexture
+ * (src/DomeLight.cpp:8-78) runs again, on the device, to the bits of the host build.  The
+ * update commits or does nothing: a texture whose Distribution1D integral is not positive
+ * and finite is refused as by mrt_scene_add_light (MRT_ERR_INVALID), texels and tables
+ * staying as they were.  *update_ms (nullable): device time on the current device.
+ * The async form reads d_data (device memory) on `stream`; a refused update is counted on
+ * the device instead.  Afterwards the host copy is stale (the tables after either form, the
+ * texels after the async one): mrt_scene_dome_export, mrt_scene_dome_export_derived,
+ * mrt_scene_add_light, a re-upload and an upload to a second device first read it back. */
+int mrt_scene_update_texture(mrt_scene* s, int32_t texture, const float* data, float* update_ms);
+int mrt_scene_update_texture_async(mrt_scene* s, int32_t texture, const float* d_data, void* stream);
+/* *rejected: async texture updates refused since the last call (one device word is read and
+ * cleared; the caller has synchronised the streams it used); 0 for a scene not uploaded. */
+int mrt_scene_texture_update_status(mrt_scene* s, int32_t* rejected);
+/* The derived tables of the device sampler mrt_scene_dome_export leaves out (DomeLight has no
+ * counterpart): rad[(nu+1)*(nv+1)*4], guide_u[nu+1], guide_v[nu*(nv+1)]. */
+int mrt_scene_dome_export_derived(const mrt_scene* s, int32_t light, float* rad, int32_t* guide_u,
+                                  int32_t* guide_v);
+/* How many times this scene has been uploaded to a device (one per replica made); no
+ * reference counterpart: a probe for tests. */
+int mrt_scene_upload_count(const mrt_scene* s);
+
 /* ---- frame entry: Scene::raytraceImage(Camera*, Image*) (src/Scene.cpp:85-217).
  * Synchronous, host buffers: rgb (W*H*3 floats, before Map) and rgb8 (W*H*3,
  * after Image::Map; nullable); hits (W*H, nullable).  1 spp primary + shadow. */

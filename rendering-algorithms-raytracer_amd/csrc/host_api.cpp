@@ -191,6 +191,123 @@ int instances_check(const Scene& S, const int32_t* ids, int32_t first, int32_t n
     return MRT_OK;
 }
 
+// mrt_scene_add_light / mrt_scene_update_lights: Light as the kernels read it.
+// Light::setFastShadows(false): a point light's "full method" (src/PointLight.cpp:49-70)
+// sets sampleHit.t = distance and then loops while sampleHit.t < distance: it never
+// traces, so the light casts no shadow -- exactly cast_shadows = 0.  The rectangle and
+// dome lights walk through refractive hits (src/RectangleLight.cpp:93-116,
+// src/DomeLight.cpp:123-145; Shader::transmit).
+DevLight make_light(const mrt_light& l, int32_t dome) {
+    DevLight d;
+    memset(&d, 0, sizeof d);
+    d.dome = dome;
+    d.type = l.type;
+    memcpy(d.pos, l.pos, 12); memcpy(d.v1, l.v1, 12); memcpy(d.v2, l.v2, 12); memcpy(d.v3, l.v3, 12);
+    d.samples = l.samples < 1 ? 1 : l.samples;
+    d.noise = l.noise_threshold;
+    d.cast_shadows = l.cast_shadows && !(l.transparent_shadows && l.type == MRT_POINT_LIGHT);
+    d.transparent = l.transparent_shadows && l.type != MRT_POINT_LIGHT ? 1 : 0;
+    d.power = l.power;
+    if (l.type == MRT_RECT_LIGHT) {
+        // RectangleLight::setPower (src/RectangleLight.cpp:14-40)
+        const uint16_t* RS = host_rsqrt_table();
+        v3 v1 = mk(l.v1[0], l.v1[1], l.v1[2]);
+        v3 e0 = sub(mk(l.v2[0], l.v2[1], l.v2[2]), v1), e1 = sub(mk(l.v3[0], l.v3[1], l.v3[2]), v1);
+        float recip = 1.0f, sq;
+        if (fabsf(dot(e0, e1)) < 0.001f) sq = dot(e0, e0) * dot(e1, e1);
+        else { v3 c = cross(e0, e1); sq = dot(c, c); }
+        if (sq > 0.001f) recip = rsqrt_nr(sq, RS);
+        d.power = l.power * recip;
+    }
+    return d;
+}
+
+void set_material_base(DevMaterial& d, const mrt_material& m) {
+    memcpy(d.kd, m.kd, 12); memcpy(d.ka, m.ka, 12); memcpy(d.ks, m.ks, 12);
+    d.spec_exp = m.spec_exp; d.spec_amt = m.spec_amt;
+    memcpy(d.le, m.le, 12);
+    d.emitted = m.emitted;
+    d.emitter = (d.emitted > 0.0f || (d.le[0] + d.le[1]) + d.le[2] > 0.0f) ? 1 : 0;   // src/Blinn.cpp:47
+    if (d.type != MRT_BLINN) { d.le[0] = d.le[1] = d.le[2] = 0.f; d.emitted = 0.f; d.emitter = 0; }
+}
+
+// mrt_scene_update_lights / _async (mrt_relight.hip): n lights that keep what shapes the replica
+int lights_check(const Scene& S, const mrt_light* lights, int32_t n) {
+    if (!lights) { set_error("update_lights: null lights"); return MRT_ERR_INVALID; }
+    if (n < 0 || (size_t)n != S.lights.size()) {
+        set_error("update_lights: " + std::to_string(n) + " lights given, the scene has " + std::to_string(S.lights.size()) +
+                  " (the count is fixed: add lights with mrt_scene_add_light)");
+        return MRT_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        const mrt_light& a = S.light_args[(size_t)i];
+        const mrt_light& b = lights[i];
+        const char* field = nullptr;
+        if (b.type != a.type) field = "type";
+        else if (a.type == MRT_DOME_LIGHT && b.texture != a.texture) field = "texture";
+        else if ((b.transparent_shadows != 0) != (a.transparent_shadows != 0)) field = "transparent_shadows";
+        if (field) {
+            set_error("update_lights: light " + std::to_string(i) + " changes its " + field +
+                      " (it decides which kernels the scene runs: mrt_scene_add_light on a new scene)");
+            return MRT_ERR_INVALID;
+        }
+    }
+    return MRT_OK;
+}
+
+// mrt_scene_update_material / _async (mrt_relight.hip)
+int material_check(const Scene& S, int material, const mrt_material* m) {
+    if (!m) { set_error("update_material: null material"); return MRT_ERR_INVALID; }
+    if (material < 0 || material >= (int)S.materials.size()) {
+        set_error("update_material: bad material id " + std::to_string(material) + " (the scene has " +
+                  std::to_string(S.materials.size()) + " materials)");
+        return MRT_ERR_INVALID;
+    }
+    if (m->type != S.materials[(size_t)material].type) {
+        set_error("update_material: material " + std::to_string(material) + " changes its type (Lambert / Blinn is fixed)");
+        return MRT_ERR_INVALID;
+    }
+    return MRT_OK;
+}
+
+// mrt_scene_update_texture / _async (mrt_relight.hip)
+int texture_check(const Scene& S, int32_t texture, const float* data) {
+    if (!data) { set_error("update_texture: null texels"); return MRT_ERR_INVALID; }
+    if (texture < 0 || texture >= (int32_t)S.textures.size()) {
+        set_error("update_texture: bad texture id " + std::to_string(texture) + " (the scene has " +
+                  std::to_string(S.textures.size()) + " textures)");
+        return MRT_ERR_INVALID;
+    }
+    return MRT_OK;
+}
+
+std::vector<int32_t> domes_of_texture(const Scene& S, int32_t texture) {
+    std::vector<int32_t> out;
+    for (size_t i = 0; i < S.domes.size(); i++)
+        if (S.domes[i].tex == texture) out.push_back((int32_t)i);
+    return out;
+}
+
+int update_texture_host(Scene& S, int32_t texture, const float* data) {
+    Texture& T = S.textures[(size_t)texture];
+    std::vector<float> old(data, data + T.rgb.size());
+    old.swap(T.rgb);
+    const std::vector<int32_t> ids = domes_of_texture(S, texture);
+    std::vector<DomeTables> built(ids.size());
+    for (size_t k = 0; k < ids.size(); k++) {
+        std::string err;
+        const int rc = build_dome(T, built[k], err);
+        if (rc) {
+            old.swap(T.rgb);
+            set_error("update_texture: " + err);
+            return rc;
+        }
+        built[k].tex = texture;
+    }
+    for (size_t k = 0; k < ids.size(); k++) S.domes[(size_t)ids[k]] = std::move(built[k]);
+    return MRT_OK;
+}
+
 }  // namespace mrt
 
 using namespace mrt;
@@ -207,19 +324,14 @@ int mrt_scene_add_material(mrt_scene* s, const mrt_material* m) {
     if (s->impl.materials.size() >= (size_t)kMaxMaterials) { set_error("too many materials"); return MRT_ERR_INVALID; }
     DevMaterial d;
     d.type = m->type;
-    memcpy(d.kd, m->kd, 12); memcpy(d.ka, m->ka, 12); memcpy(d.ks, m->ks, 12);
-    d.spec_exp = m->spec_exp; d.spec_amt = m->spec_amt;
+    set_material_base(d, *m);
     d.reflect = 0.f; d.refract = 0.f; d.ior = 1.5f; d.gloss = 1.f;   // Blinn defaults (src/Blinn.h:11-22)
     d.disperse = 0; d.ior3[0] = d.ior3[1] = d.ior3[2] = 1.5f;
     d.translucency = 0.f;
-    memcpy(d.le, m->le, 12);
-    d.emitted = m->emitted;
     d.sample_env = 1;                                                 // Material::Material, src/Material.cpp:6
     d.env = -1;                                                       // m_envMap NULL, m_envExposure 1 (:4)
     d.env_exposure = 1.f;
     for (int k = 0; k < 6; k++) d.maps[k] = -1;                       // no maps (src/Material.cpp:4-5)
-    d.emitter = (d.emitted > 0.0f || (d.le[0] + d.le[1]) + d.le[2] > 0.0f) ? 1 : 0;   // src/Blinn.cpp:47
-    if (m->type != MRT_BLINN) { d.le[0] = d.le[1] = d.le[2] = 0.f; d.emitted = 0.f; d.emitter = 0; }
     s->impl.materials.push_back(d);
     s->impl.dev_dirty = true;
     return (int)s->impl.materials.size() - 1;
@@ -231,14 +343,7 @@ int mrt_scene_add_light(mrt_scene* s, const mrt_light* l) {
         return MRT_ERR_INVALID;
     }
     if (s->impl.lights.size() >= (size_t)kMaxLights) { set_error("too many lights"); return MRT_ERR_INVALID; }
-    // Light::setFastShadows(false).  A point light's "full method" (src/PointLight.cpp:49-70)
-    // sets sampleHit.t = distance and then loops while sampleHit.t < distance: it never
-    // traces, so the light casts no shadow -- exactly cast_shadows = 0.  The rectangle and
-    // dome lights walk through refractive hits (src/RectangleLight.cpp:93-116,
-    // src/DomeLight.cpp:123-145; Shader::transmit).
-    DevLight d;
-    memset(&d, 0, sizeof d);
-    d.dome = -1;
+    int32_t dome = -1;
     if (l->type == MRT_DOME_LIGHT) {
         // DomeLight::setTexture (src/DomeLight.cpp:8-78): tables built now, on the host
         if (l->texture < 0 || l->texture >= (int32_t)s->impl.textures.size() ||
@@ -246,33 +351,17 @@ int mrt_scene_add_light(mrt_scene* s, const mrt_light* l) {
             set_error("dome light needs an RGB / HDR texture id from mrt_scene_add_texture");
             return MRT_ERR_INVALID;
         }
+        if (const int rc = sync_host(s->impl)) return rc;   // the texels an async texture update left on the device
         DomeTables t;
         std::string err;
         const int rc = build_dome(s->impl.textures[l->texture], t, err);
         if (rc) { set_error(err); return rc; }
         t.tex = l->texture;
-        d.dome = (int32_t)s->impl.domes.size();
+        dome = (int32_t)s->impl.domes.size();
         s->impl.domes.push_back(std::move(t));
     }
-    d.type = l->type;
-    memcpy(d.pos, l->pos, 12); memcpy(d.v1, l->v1, 12); memcpy(d.v2, l->v2, 12); memcpy(d.v3, l->v3, 12);
-    d.samples = l->samples < 1 ? 1 : l->samples;
-    d.noise = l->noise_threshold;
-    d.cast_shadows = l->cast_shadows && !(l->transparent_shadows && l->type == MRT_POINT_LIGHT);
-    d.transparent = l->transparent_shadows && l->type != MRT_POINT_LIGHT ? 1 : 0;
-    d.power = l->power;
-    if (l->type == MRT_RECT_LIGHT) {
-        // RectangleLight::setPower (src/RectangleLight.cpp:14-40)
-        const uint16_t* RS = host_rsqrt_table();
-        v3 v1 = mk(l->v1[0], l->v1[1], l->v1[2]);
-        v3 e0 = sub(mk(l->v2[0], l->v2[1], l->v2[2]), v1), e1 = sub(mk(l->v3[0], l->v3[1], l->v3[2]), v1);
-        float recip = 1.0f, sq;
-        if (fabsf(dot(e0, e1)) < 0.001f) sq = dot(e0, e0) * dot(e1, e1);
-        else { v3 c = cross(e0, e1); sq = dot(c, c); }
-        if (sq > 0.001f) recip = rsqrt_nr(sq, RS);
-        d.power = l->power * recip;
-    }
-    s->impl.lights.push_back(d);
+    s->impl.lights.push_back(make_light(*l, dome));
+    s->impl.light_args.push_back(*l);
     s->impl.dev_dirty = true;
     return (int)s->impl.lights.size() - 1;
 }
@@ -462,12 +551,29 @@ int mrt_scene_dome_export(const mrt_scene* s, int32_t light, float* cdf_u, float
         set_error("not a dome light / bad argument");
         return MRT_ERR_INVALID;
     }
+    // after a device texture update: the tables the device built, read back
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
     auto put = [](const std::vector<float>& v, float* dst) { memcpy(dst, v.data(), v.size() * sizeof(float)); };
     put(t->cdf_u, cdf_u); put(t->func_u, func_u); put(t->cdf_v, cdf_v); put(t->func_v, func_v);
     put(t->int_v, func_int);
     func_int[t->nu] = t->int_u;
     put(t->cos_u, cos_u); put(t->sin_u, sin_u); put(t->cos_v, cos_v); put(t->sin_v, sin_v);
     return MRT_OK;
+}
+
+int mrt_scene_dome_export_derived(const mrt_scene* s, int32_t light, float* rad, int32_t* guide_u, int32_t* guide_v) {
+    const DomeTables* t = dome_of(s, light);
+    if (!t || !rad || !guide_u || !guide_v) { set_error("not a dome light / bad argument"); return MRT_ERR_INVALID; }
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
+    memcpy(rad, t->rad.data(), t->rad.size() * sizeof(float));
+    memcpy(guide_u, t->guide_u.data(), t->guide_u.size() * sizeof(int32_t));
+    memcpy(guide_v, t->guide_v.data(), t->guide_v.size() * sizeof(int32_t));
+    return MRT_OK;
+}
+
+int mrt_scene_upload_count(const mrt_scene* s) {
+    if (!s) { set_error("null scene"); return MRT_ERR_INVALID; }
+    return s->impl.upload_count;
 }
 
 int mrt_scene_add_obj(mrt_scene* s, const char* path, const float* ctm16, int material) {

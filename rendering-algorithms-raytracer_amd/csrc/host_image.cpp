@@ -231,6 +231,14 @@ void scene_flags(const Scene& s, DeviceImage& g) {
                 for (int a = 0; a < 3; a++) g.boxes_ordered &= q.box[a * 4 + i] <= q.box[12 + a * 4 + i];
     }
     if (!g.DN.empty()) root_box(g.DN[0], g.bb_lo, g.bb_hi);
+    shading_flags(s, g);
+}
+
+}  // namespace
+
+// what the launches ask of a scene's lights and materials (scene_flags at upload;
+// mrt_scene_update_lights / _material on every replica's ImageInfo afterwards)
+void shading_flags(const Scene& s, ImageInfo& g) {
     g.point_only = true;
     g.dome = false;
     // transparent shadows: the walk is compiled into the fused chain kernels only (it
@@ -254,6 +262,8 @@ void scene_flags(const Scene& s, DeviceImage& g) {
     if (s.path_trace) g.recursive = 2;
     if (g.transparent && !g.recursive) g.recursive = 1;
 }
+
+namespace {
 
 // mrt_scene_info.device_bytes: every array upload_scene copies (an empty one counts 0)
 size_t image_bytes(const Scene& s, const DeviceImage& g) {

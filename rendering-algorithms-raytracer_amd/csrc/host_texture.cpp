@@ -169,6 +169,11 @@ int load_hdr(const char* path, int& W, int& H, std::vector<float>* rgb, std::str
     return MRT_OK;
 }
 
+void dome_sin_theta(int nv, std::vector<float>& out) {
+    out.resize((size_t)nv);
+    for (int i = 0; i < nv; i++) out[i] = sinf(kPI * (float)(i + .5) / (float)nv);
+}
+
 // DomeLight::setTexture (src/DomeLight.cpp:8-78)
 int build_dome(const Texture& t, DomeTables& d, std::string& err) {
     const int nu = t.W, nv = t.H;
@@ -183,8 +188,8 @@ int build_dome(const Texture& t, DomeTables& d, std::string& err) {
             img[(size_t)u * nv + v] = ((L.x + L.y) + L.z) * 0.333333f;  // Vector3::average
         }
     }
-    std::vector<float> sin_theta(nv);
-    for (int i = 0; i < nv; i++) sin_theta[i] = sinf(kPI * (float)(i + .5) / (float)nv);
+    std::vector<float> sin_theta;
+    dome_sin_theta(nv, sin_theta);
     d.func_v.resize((size_t)nu * nv);
     d.cdf_v.resize((size_t)nu * (nv + 1));
     d.int_v.resize(nu);

@@ -265,6 +265,19 @@ struct DeviceState : ImageInfo {
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
     int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS
     std::vector<int32_t> mesh_prim0;       // per mesh: its first world prim (its triangles follow in order), -1 = none
+    // relight (mrt_relight.hip): the records upload_scene wrote to domes / texs (their device
+    // pointers), and what the first texture update on this replica makes
+    std::vector<DevDome> dome_recs;
+    std::vector<DevTexture> tex_recs;
+    bool relight_ready = false;
+    std::vector<float*> relight_sin;      // per dome: sin(theta) of its nv rows (dome_sin_theta)
+    std::vector<float*> relight_int;      // per dome: int_v[nu], then int_u (what mrt_scene_dome_export adds to the tables)
+    float* relight_tab = nullptr;         // scratch tables of one dome build, sized by the largest dome
+    size_t relight_tab_cap = 0;           //   floats
+    uint32_t* relight_status = nullptr;   // word 0: rejected async updates since the last status call; word 1: the last build passed
+    float* relight_stage = nullptr;       // the synchronous entry's texels on the device
+    size_t relight_stage_cap = 0;         //   floats
+    hipEvent_t relight_ev0 = nullptr, relight_ev1 = nullptr;
     int cus = 0;
     int wall_khz = 0;            // wall_clock64() rate
     // per-stream launch scratch: frames on different streams are in flight at once
@@ -283,6 +296,9 @@ struct DeviceState : ImageInfo {
 void free_replicas(Scene& s);
 int get_ctx(DeviceState& d, hipStream_t stream, StreamCtx*& out);   // scratch context of `stream`
 int ensure_device(Scene& s, int device);                            // the scene's replica on `device` becomes s.dev
+// mrt_relight.hip: the texels of Scene::host_tex_stale and the DomeTables of host_dome_stale from
+// replica d (sync_host's part for texture updates; the caller has synchronised the device)
+int relight_read_back(Scene& s, DeviceState& d);
 
 }  // namespace mrt
 #endif   // __HIPCC__

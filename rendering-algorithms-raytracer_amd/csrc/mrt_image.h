@@ -84,5 +84,7 @@ struct DeviceImage : ImageInfo {
 
 int build_image(const Scene& s, DeviceImage& img, std::string& err);   // MRT_OK, or MRT_ERR_OVERFLOW with err
 void root_box(const QNode& root, float lo[3], float hi[3]);            // union of the root's used slot boxes (finite values)
+// point_only, dome, transparent, recursive, pow_spec and disperse of g from s.lights, s.materials and s.path_trace
+void shading_flags(const Scene& s, ImageInfo& g);
 
 }  // namespace mrt

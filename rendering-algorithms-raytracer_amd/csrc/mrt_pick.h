@@ -77,5 +77,20 @@ LightFn pick_light_points(bool c, bool f, bool inst, bool check, bool xp);
 // traversal: one instantiation each; the trace between them is pick_shadow's)
 LightPassFn pick_light_gen();
 LightPassFn pick_light_resolve();
+// mrt_relight.hip: the device build of a dome light's tables after mrt_scene_update_texture (one
+// instantiation each) -- the column scans, the column normalisation with its guide tables, the
+// row scan with the int_u test, the rad cells, the gated commits of the tables and the texels --
+// and the store of light / material records that arrive as a kernel argument
+struct DomeBuild;
+using DomeFn = void (*)(DomeBuild);
+struct RelightWords;
+using RelightFn = void (*)(unsigned*, RelightWords, int);
+DomeFn pick_dome_scan();
+DomeFn pick_dome_guide();
+DomeFn pick_dome_row();
+DomeFn pick_dome_rad();
+DomeFn pick_dome_commit();
+DomeFn pick_tex_commit();
+RelightFn pick_relight_store();
 
 }  // namespace mrt

@@ -495,6 +495,7 @@ int sync_host(Scene& s, bool meshes_only) {
     HIP_OK(hipDeviceSynchronize());
     int rc;
     if (s.host_bvh_stale && !meshes_only && (rc = read_tree(*d, d->world, d->node_perm, s.nodes, s.leaves))) return rc;
+    if (!meshes_only && (rc = relight_read_back(s, *d))) return rc;   // texels and dome tables of a device texture update
     std::vector<float4> buf;
     auto read3 = [&](std::vector<v3>& dst, const float4* src) -> int {
         buf.resize(dst.size());

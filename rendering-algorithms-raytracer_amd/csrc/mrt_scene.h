@@ -75,6 +75,7 @@ struct Scene {
     std::vector<Mesh> meshes;
     std::vector<DevMaterial> materials;
     std::vector<DevLight> lights;
+    std::vector<mrt_light> light_args;   // what mrt_scene_add_light was given, per light (mrt_scene_update_lights compares)
     std::vector<Texture> textures;
     std::vector<DomeTables> domes;
     int32_t env_tex = -1;           // Scene::m_envMap (-1: background colour)
@@ -124,9 +125,15 @@ struct Scene {
     // After mrt_scene_deform_mesh on an uploaded scene the nodes and leaves of these BLASes
     // are behind the replica's (and with them the boxes of their instances: host_inst_stale).
     std::vector<int32_t> host_blas_stale;
+    // After mrt_scene_update_texture on an uploaded scene the DomeTables of these domes (indices
+    // into `domes`) are behind the replica's, which its kernels rebuilt (mrt_relight.hip), and
+    // after the async form the texels of these textures too.
+    std::vector<int32_t> host_dome_stale, host_tex_stale;
     bool host_stale() const {
-        return host_bvh_stale || !host_mesh_stale.empty() || host_inst_stale || !host_blas_stale.empty();
+        return host_bvh_stale || !host_mesh_stale.empty() || host_inst_stale || !host_blas_stale.empty() ||
+               !host_dome_stale.empty() || !host_tex_stale.empty();
     }
+    int upload_count = 0;   // upload_scene calls (mrt_scene_upload_count)
 
     // device replicas (one per HIP device used, mrt_render_opts.devices); `dev` is
     // the one the last call used.  dev_dirty: the host scene changed, every
@@ -180,7 +187,26 @@ enum { kDeformWorld = 0, kDeformBlas = 1, kDeformMotion = 2 };
 int deform_check(const Scene& s, int mesh, const float* verts, const float* verts2, bool has_verts2,
                  const float* normals, int* kind);
 void deform_set_motion(Mesh& m, const float* verts2);
+// host_api.cpp: the mrt_light -> DevLight conversion of mrt_scene_add_light (the rectangle light's
+// setPower area scaling, the samples < 1 clamp, the point-light cast_shadows rule); dome: the
+// light's DomeTables index (-1: not a dome light)
+DevLight make_light(const mrt_light& l, int32_t dome);
+// host_api.cpp: the mrt_material fields into d (what mrt_scene_add_material sets of them: kd, ka,
+// ks, spec_exp, spec_amt, le, emitted and the derived emitter; a Lambert emits nothing)
+void set_material_base(DevMaterial& d, const mrt_material& m);
+// host_api.cpp: the argument checks of mrt_scene_update_lights / _material / _texture, each
+// refusal with its own text and before any device call
+int lights_check(const Scene& s, const mrt_light* lights, int32_t n);
+int material_check(const Scene& s, int material, const mrt_material* m);
+int texture_check(const Scene& s, int32_t texture, const float* data);
+// the domes (indices into Scene::domes) that texture `texture` feeds
+std::vector<int32_t> domes_of_texture(const Scene& s, int32_t texture);
+// mrt_scene_update_texture on the host copy: new texels, build_dome for every dome the texture
+// feeds; on a refusal the old texels are back and nothing changed
+int update_texture_host(Scene& s, int32_t texture, const float* data);
 // host_texture.cpp
+// sin(theta) of row i's centre, i = 0 .. nv - 1: build_dome's weights (they depend on nv only)
+void dome_sin_theta(int nv, std::vector<float>& out);
 int load_hdr(const char* path, int& W, int& H, std::vector<float>* rgb, std::string& err);
 int build_dome(const Texture& t, DomeTables& d, std::string& err);
 // RawImage::loadImage (TGA / PPM / HDR by extension); data == nullptr: size + type only

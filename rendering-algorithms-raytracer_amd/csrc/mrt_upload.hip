@@ -145,6 +145,7 @@ int ensure_device(Scene& s, int device) {
 // device's properties.
 static int upload_scene(Scene& s, DeviceState& d, int device) {
     d.device = device;
+    s.upload_count++;
     HIP_OK(hipSetDevice(device));
     DeviceImage g;
     std::string err;
@@ -181,6 +182,8 @@ static int upload_scene(Scene& s, DeviceState& d, int device) {
     std::vector<DevTexture> DT(s.textures.size());
     for (size_t i = 0; i < DT.size(); i++) DT[i] = DevTexture{dtex[i], s.textures[i].W, s.textures[i].H, s.textures[i].type, 0};
     if ((rc = up(d.texs, DT))) return rc;
+    d.dome_recs = DD;   // mrt_relight.hip writes through these pointers
+    d.tex_recs = DT;
     if (g.any_uv && ((rc = up(d.puv, g.PUV)) || (rc = up(d.uvs, g.UV)) || (rc = up(d.tans, g.TN)) || (rc = up(d.btans, g.BTN))))
         return rc;
     if (g.has_mb && ((rc = up(d.verts2, g.V2)) || (rc = up(d.pflags, g.PF)))) return rc;

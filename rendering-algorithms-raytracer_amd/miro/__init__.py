@@ -669,6 +669,7 @@ class Scene:
             m16 = np.ascontiguousarray(item.matrix, np.float32).reshape(16)
             check(L.mrt_scene_add_instance(self._h, blas[key], m16.ctypes.data_as(C.POINTER(C.c_float))), "instance")
         tex_ids = {}
+        tex_shapes = {}   # texture id -> (H, W, channels): what updateTexture accepts
 
         def tex_id(t):
             if t is None:
@@ -681,6 +682,7 @@ class Scene:
                 tex_ids[id(t)] = check(L.mrt_scene_add_texture_typed(self._h, a.ctypes.data_as(C.POINTER(C.c_float)),
                                                                      img.m_width, img.m_height,
                                                                      getattr(img, "m_imageType", TEX_HDR)), "add_texture")
+                tex_shapes[tex_ids[id(t)]] = (img.m_height, img.m_width, _CHANNELS[getattr(img, "m_imageType", TEX_HDR)])
             return tex_ids[id(t)]
 
         for key, mid in mats.items():   # Material::set*Map
@@ -693,8 +695,10 @@ class Scene:
                 check(L.mrt_scene_set_material_env_map(self._h, mid, tex_id(mat.envMap), mat.envExposure),
                       "material env map")
 
+        self._mat_ids, self._mat_objs, self._tex_ids, self._tex_shapes = mats, mat_objs, tex_ids, tex_shapes
         for light in self._lights:
-            lc = light._c(tex_id(getattr(light, "texture", None)))
+            tex_id(getattr(light, "texture", None))   # DomeLight::setTexture: the texture joins the scene
+            lc = self._light_c(light)
             check(L.mrt_scene_add_light(self._h, C.byref(lc)), "add_light")
         if self.m_envMap is not None:
             check(L.mrt_scene_set_env_map(self._h, tex_id(self.m_envMap), self.m_envExposure), "env map")
@@ -710,6 +714,12 @@ class Scene:
         check(L.mrt_scene_bvh_info(self._h, C.byref(info)), "bvh_info")
         self.bvh_info = {k: getattr(info, k) for k, _ in info._fields_}
         return self.bvh_info
+
+    def _light_c(self, light):
+        """A Light object as mrt_light: the conversion preCalc and updateLights share (a dome
+        light's texture as the id preCalc gave it)."""
+        t = getattr(light, "texture", None)
+        return light._c(-1 if t is None else self._tex_ids[id(t)])
 
     def mesh_arrays(self, mesh_id: int):
         L = lib()
@@ -762,6 +772,104 @@ class Scene:
                                          lt.ctypes.data_as(C.POINTER(C.c_float)),
                                          lp.ctypes.data_as(C.POINTER(C.c_int32))), "bvh_export")
         return nb, nc, lt, lp
+
+    def domeTablesDerived(self, light: int):
+        """The derived tables of dome light `light` dome_tables leaves out: rad ((nv + 1, nu + 1, 4)),
+        guide_u (nu + 1), guide_v ((nu, nv + 1)) (mrt_scene_dome_export_derived)."""
+        L = lib()
+        nu, nv = C.c_int32(), C.c_int32()
+        check(L.mrt_scene_dome_info(self.handle, int(light), C.byref(nu), C.byref(nv)), "dome_info")
+        nu, nv = nu.value, nv.value
+        out = {"rad": np.zeros((nv + 1, nu + 1, 4), np.float32), "guide_u": np.zeros(nu + 1, np.int32),
+               "guide_v": np.zeros((nu, nv + 1), np.int32)}
+        check(L.mrt_scene_dome_export_derived(self.handle, int(light), out["rad"].ctypes.data_as(C.POINTER(C.c_float)),
+                                              out["guide_u"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                              out["guide_v"].ctypes.data_as(C.POINTER(C.c_int32))), "dome_export_derived")
+        return out
+
+    def uploadCount(self):
+        """How many times the built scene has been uploaded to a device (mrt_scene_upload_count)."""
+        return check(lib().mrt_scene_upload_count(self.handle), "uploadCount")
+
+    # -- lights, materials and texels that change between frames (no reference counterpart: its
+    #    setters act on live objects; here the replica is updated in place, without a re-upload)
+    def _stream_arg(self, stream):
+        import torch
+        return (stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))).cuda_stream
+
+    def updateLights(self, stream=None, asynchronous=False):
+        """The current fields of the Light objects the scene was built from, in place
+        (mrt_scene_update_lights): position, vertices, power, samples, noise threshold and
+        castShadows may have changed; type, texture and fastShadows may not.  asynchronous=True
+        (or a `stream`): mrt_scene_update_lights_async on `stream` (a torch stream; default: the
+        current one), without a synchronisation; the scene is uploaded first if it is not."""
+        L = lib()
+        n = len(self._lights)
+        arr = (_lib.mrt_light * max(n, 1))(*[self._light_c(l) for l in self._lights])
+        if asynchronous or stream is not None:
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            check(L.mrt_scene_update_lights_async(self.handle, arr, n, self._stream_arg(stream)), "updateLights")
+        else:
+            check(L.mrt_scene_update_lights(self.handle, arr, n), "updateLights")
+
+    def updateMaterial(self, material, stream=None, asynchronous=False):
+        """The current kd, ka, ks, specExp, specAmt, Le and lightEmitted of `material` (a material
+        object the scene was built with), in place (mrt_scene_update_material); everything its
+        other setters cover stays.  asynchronous / stream: as updateLights."""
+        L = lib()
+        if id(material) not in getattr(self, "_mat_ids", {}):
+            raise MRTError("updateMaterial: not a material of this scene (preCalc() assigns the ids)")
+        mid, m = self._mat_ids[id(material)], material._c()
+        if asynchronous or stream is not None:
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            check(L.mrt_scene_update_material_async(self.handle, mid, C.byref(m), self._stream_arg(stream)), "updateMaterial")
+        else:
+            check(L.mrt_scene_update_material(self.handle, mid, C.byref(m)), "updateMaterial")
+
+    def textureId(self, texture):
+        """The id preCalc gave a Texture object (an int passes through)."""
+        if isinstance(texture, (int, np.integer)):
+            return int(texture)
+        if id(texture) not in getattr(self, "_tex_ids", {}):
+            raise MRTError("not a texture of this scene (preCalc() assigns the ids)")
+        return self._tex_ids[id(texture)]
+
+    def updateTexture(self, texture, data, stream=None):
+        """New texels for `texture` (a Texture of the scene, or its id), same width, height and
+        type (mrt_scene_update_texture).  Environment maps and material maps read them at once;
+        for a dome light of this texture DomeLight::setTexture runs again on the device.  A numpy
+        array ((H, W, channels) float32) goes through the synchronous entry, which returns the
+        device time in ms (0.0 for a scene not uploaded: the host rebuilds) and raises for a
+        dome texture without positive radiance, everything staying as it was.  A float32 torch
+        tensor on the scene's device goes through mrt_scene_update_texture_async on `stream`
+        (default: the current one) and returns None; textureUpdateStatus() reports refusals."""
+        L = lib()
+        tid = self.textureId(texture)
+        shape = getattr(self, "_tex_shapes", {}).get(tid)
+        if shape is None:
+            raise MRTError(f"updateTexture: bad texture id {tid}")
+        if tuple(data.shape) != shape:
+            raise MRTError(f"updateTexture: texels must have shape {shape} (height, width, channels), not {tuple(data.shape)}")
+        if hasattr(data, "data_ptr"):
+            import torch
+            if not (data.is_cuda and data.dtype == torch.float32 and data.is_contiguous() and data.device.index == self.device):
+                raise MRTError("updateTexture: tensors must be contiguous float32 on the scene's device")
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            check(L.mrt_scene_update_texture_async(self.handle, tid, data.data_ptr(), self._stream_arg(stream)), "updateTexture")
+            return None
+        if np.asarray(data).dtype != np.float32:
+            raise MRTError("updateTexture: texels must be float32")
+        a = np.ascontiguousarray(data, np.float32)
+        ms = C.c_float(0.0)
+        check(L.mrt_scene_update_texture(self.handle, tid, a.ctypes.data, C.byref(ms)), "updateTexture")
+        return float(ms.value)
+
+    def textureUpdateStatus(self):
+        """Async texture updates refused since the last call (mrt_scene_texture_update_status; the
+        caller has synchronised the streams it used)."""
+        n = C.c_int32(0)
+        check(lib().mrt_scene_texture_update_status(self.handle, C.byref(n)), "textureUpdateStatus")
+        return int(n.value)
 
     # -- geometry that moves between frames (no reference counterpart: it rebuilds)
     def updateMesh(self, mesh_id: int, verts, normals=None, stream=None):

@@ -36,6 +36,9 @@ EXPORTS = [
     "mrt_scene_instance_info", "mrt_scene_deform_mesh", "mrt_scene_deform_mesh_async",
     "mrt_debug_live_resources", "mrt_sample_lights", "mrt_sample_lights_async",
     "mrt_scene_light_sample_cap", "mrt_light_samples", "mrt_light_samples_async",
+    "mrt_scene_update_lights", "mrt_scene_update_lights_async", "mrt_scene_update_material",
+    "mrt_scene_update_material_async", "mrt_scene_update_texture", "mrt_scene_update_texture_async",
+    "mrt_scene_texture_update_status", "mrt_scene_dome_export_derived", "mrt_scene_upload_count",
 ]
 
 
@@ -237,6 +240,17 @@ def load():
     if hasattr(L, "mrt_scene_deform_mesh"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
         L.mrt_scene_deform_mesh.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.mrt_scene_deform_mesh_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mrt_scene_update_lights"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        vp = C.c_void_p
+        L.mrt_scene_update_lights.argtypes = [vp, vp, C.c_int32]
+        L.mrt_scene_update_lights_async.argtypes = [vp, vp, C.c_int32, vp]
+        L.mrt_scene_update_material.argtypes = [vp, C.c_int, vp]
+        L.mrt_scene_update_material_async.argtypes = [vp, C.c_int, vp, vp]
+        L.mrt_scene_update_texture.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_float)]
+        L.mrt_scene_update_texture_async.argtypes = [vp, C.c_int32, vp, vp]
+        L.mrt_scene_texture_update_status.argtypes = [vp, _ip]
+        L.mrt_scene_dome_export_derived.argtypes = [vp, C.c_int32, _fp, _ip, _ip]
+        L.mrt_scene_upload_count.argtypes = [vp]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
