@@ -352,8 +352,9 @@ int mrt_scene_upload(mrt_scene* s, int device);
  * world hierarchy on every uploaded replica of the scene: the tree keeps its topology,
  * the leaf triangles are recomputed from the vertices and every box from its children
  * (std::min / std::max merges in lane and slot order, so the result is exact and stated
- * bit for bit; DESIGN.md "Refit").  Tree quality degrades under large deformation; a
- * rebuild (mrt_scene_build_bvh) remains the remedy.
+ * bit for bit; DESIGN.md "Refit").  Tree quality degrades under large deformation:
+ * mrt_scene_rebuild_bvh (below) gives the world hierarchy a new topology on the device, and
+ * mrt_scene_bvh_cost measures when; mrt_scene_build_bvh remains the way to the best tree.
  * *refit_ms (nullable): device time of the refit kernels on the current device.
  * Scope:
  *  - world (non-instanced) meshes without mrt_scene_set_mesh_motion.  A mesh of a BLAS
@@ -405,8 +406,8 @@ int mrt_scene_update_mesh_async(mrt_scene* s, int mesh, const float* d_verts,
  *    refitted on the host: the same arithmetic.
  * New vertices for a mesh of a BLAS or a motion-blurred mesh: mrt_scene_deform_mesh.
  * Out of scope: adding or removing instances, changing an instance's BLAS, any
- * rebuild heuristic (tree quality degrades as instances travel; mrt_scene_build_bvh on a
- * new scene remains the remedy), and the shim. */
+ * automatic rebuild (tree quality degrades as instances travel: mrt_scene_rebuild_bvh
+ * below), and the shim. */
 int mrt_scene_update_instances(mrt_scene* s, const int32_t* ids, int32_t n,
                                const float* m16s, float* refit_ms);
 /* The same for the contiguous range [first, first + n) with the matrices on the device,
@@ -462,6 +463,48 @@ int mrt_scene_deform_mesh(mrt_scene* s, int mesh, const float* verts, const floa
  * a re-upload and an upload to a second device first read the device state back. */
 int mrt_scene_deform_mesh_async(mrt_scene* s, int mesh, const float* d_verts, const float* d_verts2,
                                 const float* d_normals, void* stream);
+
+/* ---- the world hierarchy rebuilt on the device (no reference counterpart: Scene::preCalc ->
+ * BVH::build on the host is what the reference does between frames; DESIGN.md "Rebuild").
+ * A new topology for the WORLD hierarchy from the lanes its packets hold now -- plain
+ * triangles, ProxyObject lanes and MBObject lanes -- with no re-upload: a lane's box is the
+ * one a refit gives it; its key is the 30-bit Morton code of the box centre in the root box
+ * over its current position (4 * packet + lane); the sorted lanes fill packets four at a
+ * time, triangle data and prim words moved as they are; a binary radix tree over the packet
+ * keys (Karras 2012) is cut into 4-wide nodes, two bit levels per node.  Hit ids, BLASes,
+ * instance records, PrimShade records, vertices and every other array stay.  The result is a
+ * function of the input alone and is stated by mrt_scene_bvh_export (nodes numbered breadth
+ * first).  The tree is a Morton tree: worse than mrt_scene_build_bvh's on the geometry that
+ * one was built for.  Against a refitted tree it is expected to win where objects have changed
+ * places under the world tree (64 instances with permuted positions: the frame 26% faster)
+ * and measured slower where one mesh of large triangles deforms (DESIGN.md "Rebuild" has both
+ * tables): mrt_scene_bvh_cost and a timed frame decide.
+ * Conventions of mrt_scene_update_mesh / _async: everything is checked before any device call
+ * and before any change (MRT_ERR_NOT_BUILT for an unbuilt scene, MRT_ERR_INVALID for a null
+ * scene or a hierarchy from mrt_scene_bvh_import, MRT_ERR_OVERFLOW when the node array the
+ * rebuilt tree may need would pass 4 GiB); the synchronous form acts on every uploaded
+ * replica and reports in *rebuild_ms (nullable) the device time on the current one; a scene
+ * that is built but not uploaded (or due for a re-upload) is rebuilt on the host by the same
+ * rule.  The first rebuild of a replica allocates its scratch and, where the new tree may
+ * need more nodes than the world's range holds, grows the node array once.  A rebuilt replica
+ * does not take the LDS top-node walk (lds_nodes) until it is uploaded again.
+ * mrt_scene_bvh_info reports the new nodes and leaves; bin_*, max_depth and build_ms stay the
+ * host build's. */
+int mrt_scene_rebuild_bvh(mrt_scene* s, float* rebuild_ms);
+/* The same enqueued on `stream`, never synchronising after the first rebuild of a replica.
+ * That first one allocates and, where the node array has to grow, waits for the device once
+ * (hipDeviceSynchronize) and copies the nodes into the larger array before it enqueues: call
+ * it once outside a stream capture and outside a latency-critical frame.  It needs the scene uploaded to exactly one device (else MRT_ERR_INVALID).  The
+ * node count and the topology are then known on the device alone: mrt_scene_bvh_export,
+ * mrt_scene_bvh_info, mrt_scene_bvh_cost, the next refit of any kind, a re-upload and an upload
+ * to a second device first read them back, synchronising once; renders and ray queries need
+ * nothing from the host. */
+int mrt_scene_rebuild_bvh_async(mrt_scene* s, void* stream);
+/* The measure a caller decides with, in double on the host over the canonical arrays (read
+ * back first after a device refit or rebuild): the sum over every used node slot of
+ * area(slot box) / area(root box), an inner slot once and a leaf slot once per lane of its
+ * packet; the root box is the merge of node 0's used slots; a zero root area gives 0. */
+int mrt_scene_bvh_cost(const mrt_scene* s, double* cost);
 
 /* ---- relighting in place: lights, a material's base record and the texels of a texture
  * change on the replicas without a re-upload (the setters above mark the scene for one).

@@ -804,7 +804,19 @@ int mrt_scene_build_bvh(mrt_scene* s) {
 int mrt_scene_bvh_info(const mrt_scene* s, mrt_bvh_info* info) {
     if (!s || !info) { set_error("bad argument"); return MRT_ERR_INVALID; }
     if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    // after an async rebuild: the node and packet counts the device holds, read back
+    if (s->impl.host_topo_stale)
+        if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
     *info = s->impl.info;
+    return MRT_OK;
+}
+
+int mrt_scene_bvh_cost(const mrt_scene* s, double* cost) {
+    if (!s || !cost) { set_error("bad argument"); return MRT_ERR_INVALID; }
+    if (!s->impl.built) { set_error("scene not built"); return MRT_ERR_NOT_BUILT; }
+    // after a device refit or rebuild: the arrays the device holds, read back
+    if (const int rc = sync_host(const_cast<mrt_scene*>(s)->impl)) return rc;
+    *cost = bvh_cost_host(s->impl);
     return MRT_OK;
 }
 

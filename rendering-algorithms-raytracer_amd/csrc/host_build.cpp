@@ -37,6 +37,8 @@
 #include <cmath>
 #include <string>
 
+#include "mrt_image.h"
+#include "mrt_rebuild.h"
 #include "mrt_scene.h"
 
 #define MRT_TABLE_QUAL static const
@@ -1350,6 +1352,151 @@ void refit_blas_host(Scene& s, int32_t bi) {
     refit_tree(s, B.nodes, B.leaves, B.obj_mesh, B.obj_tri, false);
     for (Instance& I : s.instances)
         if (I.blas == bi) instance_box(B.nodes[0], I.m, I.box);
+}
+
+// ------------------------------------------------------------------ rebuild
+// mrt_scene_rebuild_bvh on the host (the kernels of mrt_rebuild.hip apply the same
+// rule): the world's lanes keyed by the Morton code of their box centre in the root box and
+// their position, sorted, packed four to a packet in that order, a binary radix tree over the
+// packet keys, two bit levels of it per 4-wide node.  Triangle data and prim words move as
+// they are; nodes are numbered breadth first.
+void rebuild_host(Scene& s) {
+    float rlo[3], rhi[3];
+    root_box(s.nodes[0], rlo, rhi);
+    const std::vector<QLeaf>& old = s.leaves;
+    std::vector<Box> lane_box(4 * old.size());
+    std::vector<uint64_t> keys;
+    for (size_t li = 0; li < old.size(); li++)
+        for (int k = 0; k < 4; k++) {
+            const int32_t o = old[li].prim[k];
+            if (o < 0) continue;
+            Box b;
+            float fb[6];
+            if (fixed_lane_box(s, o, fb)) b = Box{{fb[0], fb[1], fb[2]}, {fb[3], fb[4], fb[5]}};
+            else {
+                const Mesh& m = s.meshes[(size_t)s.obj_mesh[(size_t)o]];
+                const uint32_t* f = &m.vidx[3 * (size_t)s.obj_tri[(size_t)o]];
+                b = verts_box3(m.verts[f[0]], m.verts[f[1]], m.verts[f[2]]);
+            }
+            const uint32_t pos = (uint32_t)(4 * li + (size_t)k);
+            lane_box[pos] = b;
+            keys.push_back(rb_key(b.mn, b.mx, rlo, rhi, pos));
+        }
+    std::sort(keys.begin(), keys.end());
+    const size_t n = keys.size(), P = (n + 3) / 4;
+    std::vector<QLeaf> L(P);
+    std::vector<Box> pbox(P, empty_box());
+    std::vector<uint64_t> pkey(P);
+    for (size_t p = 0; p < P; p++) {
+        memset(&L[p], 0, sizeof(QLeaf));
+        for (int k = 0; k < 4; k++) L[p].prim[k] = -1;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t src = (uint32_t)keys[i];
+        const size_t p = i >> 2, k = i & 3;
+        for (int c = 0; c < 9; c++) L[p].t[4 * c + k] = old[src >> 2].t[4 * c + (src & 3u)];
+        L[p].prim[k] = old[src >> 2].prim[src & 3u];
+        pbox[p] = merge(pbox[p], lane_box[src]);
+        if (k == 0) pkey[p] = keys[i];
+    }
+    auto new_node = [] {
+        QNode q;
+        memset(&q, 0, sizeof q);
+        for (int k = 0; k < 4; k++) q.child[k] = kEmptySlot;
+        return q;
+    };
+    std::vector<QNode> N;
+    if (P == 1) {
+        N.push_back(new_node());
+        N[0].child[0] = ~0;
+        store_slot(N[0], 0, pbox[0]);
+    } else {
+        const size_t nb = P - 1;
+        std::vector<int32_t> first(nb), last(nb), left(nb), right(nb);
+        for (size_t i = 0; i < nb; i++) {
+            int64_t f, l, g;
+            rb_karras(pkey.data(), (int64_t)P, (int64_t)i, f, l, g);
+            first[i] = (int32_t)f;
+            last[i] = (int32_t)l;
+            left[i] = rb_left(f, g);
+            right[i] = rb_right(l, g);
+        }
+        // the box of every binary node, children first
+        std::vector<Box> bbox(nb);
+        std::vector<char> done(nb, 0);
+        std::vector<int32_t> stack{0};
+        auto box_of = [&](int32_t c) { return c < 0 ? pbox[(size_t)~c] : bbox[(size_t)c]; };
+        while (!stack.empty()) {
+            const int32_t b = stack.back();
+            const int32_t l = left[(size_t)b], r = right[(size_t)b];
+            const bool lr = l < 0 || done[(size_t)l], rr = r < 0 || done[(size_t)r];
+            if (lr && rr) {
+                bbox[(size_t)b] = merge(box_of(l), box_of(r));
+                done[(size_t)b] = 1;
+                stack.pop_back();
+                continue;
+            }
+            if (!lr) stack.push_back(l);
+            if (!rr) stack.push_back(r);
+        }
+        // 4-wide nodes breadth first: roots[q] is the binary node canonical node q comes from
+        std::vector<int32_t> roots{0};
+        for (size_t q = 0; q < roots.size(); q++) {
+            int32_t kid[4];
+            const int nk = rb_children(pkey.data(), first.data(), last.data(), left.data(), right.data(), roots[q], kid);
+            QNode node = new_node();
+            for (int k = 0; k < nk; k++) {
+                if (kid[k] < 0) node.child[k] = kid[k];
+                else {
+                    node.child[k] = (int32_t)roots.size();
+                    roots.push_back(kid[k]);
+                }
+                store_slot(node, k, box_of(kid[k]));
+            }
+            N.push_back(node);
+        }
+    }
+    s.nodes.swap(N);
+    s.leaves.swap(L);
+    s.info.nodes = (int32_t)s.nodes.size();
+    s.info.leaves = (int32_t)s.leaves.size();
+    s.dev_dirty = true;
+}
+
+// mrt_scene_bvh_cost: every used slot's box area over the root box's, an inner slot once, a leaf
+// slot once per lane of its packet, in double
+double bvh_cost_host(const Scene& s) {
+    auto area = [](const double lo[3], const double hi[3]) {
+        const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
+        return 2.0 * (x * y + y * z + z * x);
+    };
+    if (s.nodes.empty()) return 0.0;
+    double rlo[3] = {1e300, 1e300, 1e300}, rhi[3] = {-1e300, -1e300, -1e300};
+    bool any = false;
+    for (int k = 0; k < 4; k++) {
+        if (s.nodes[0].child[k] == kEmptySlot) continue;
+        any = true;
+        for (int a = 0; a < 3; a++) {
+            rlo[a] = std::min(rlo[a], (double)s.nodes[0].box[4 * a + k]);
+            rhi[a] = std::max(rhi[a], (double)s.nodes[0].box[12 + 4 * a + k]);
+        }
+    }
+    const double ra = any ? area(rlo, rhi) : 0.0;
+    if (!(ra > 0.0)) return 0.0;
+    double sum = 0.0;
+    for (const QNode& q : s.nodes)
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = q.child[k];
+            if (c == kEmptySlot) continue;
+            const double lo[3] = {q.box[k], q.box[4 + k], q.box[8 + k]}, hi[3] = {q.box[12 + k], q.box[16 + k], q.box[20 + k]};
+            double w = 1.0;
+            if (c < 0) {
+                w = 0.0;
+                for (int j = 0; j < 4; j++) w += s.leaves[(size_t)~c].prim[j] >= 0 ? 1.0 : 0.0;
+            }
+            sum += w * (area(lo, hi) / ra);
+        }
+    return sum;
 }
 
 }  // namespace mrt

@@ -265,6 +265,25 @@ struct DeviceState : ImageInfo {
     hipEvent_t refit_ev0 = nullptr, refit_ev1 = nullptr;
     int32_t* refit_blas_insts = nullptr;   // instance ids grouped by BLAS
     std::vector<int32_t> mesh_prim0;       // per mesh: its first world prim (its triangles follow in order), -1 = none
+    // rebuild (mrt_rebuild.hip): what the first rebuild on this replica makes.  Dense node j of a
+    // rebuilt world tree is device node j below rb_world_nodes (the world's node range of the
+    // upload) and node rb_tail + (j - rb_world_nodes) above it: rb_extra nodes past the image's.
+    bool rebuild_ready = false;
+    bool sched_stale = false;             // the world's topology changed: the next refit makes refit_order again
+    uint32_t rb_world_nodes = 0, rb_tail = 0, rb_extra = 0;
+    uint32_t rb_cap_leaves = 0;           // packets of the world's range at the upload (the rebuilt tree uses the first P)
+    uint32_t rb_cur_leaves = 0;           //   and those in use now
+    uint64_t* rb_keys = nullptr;          // [2][4 rb_cap_leaves]: lane keys, unsorted and sorted
+    float4* rb_lane_box = nullptr;        // per lane of the range: its box (2 float4)
+    DLeaf* rb_leaves = nullptr;           // the P new packets before they are copied over the range
+    float4* rb_seg = nullptr;             // min / max segment tree over the packet boxes: 2 P boxes, packet p at P + p
+    uint64_t* rb_pkey = nullptr;          // per packet: the key of its first lane
+    uint32_t* rb_pword = nullptr;         //   and the low four bits of its child word (count - 1, proxy, check)
+    int32_t* rb_bin = nullptr;            // [4][P - 1]: first, last, left, right of the binary nodes
+    uint32_t* rb_flag = nullptr;          // [2][P - 1]: roots a 4-wide node; its dense number (exclusive scan)
+    uint32_t* rb_count = nullptr;         // the node count of the last rebuild
+    void* rb_temp = nullptr;              // rocPRIM's scratch for the sort and the scan
+    size_t rb_temp_bytes = 0;
     // relight (mrt_relight.hip): the records upload_scene wrote to domes / texs (their device
     // pointers), and what the first texture update on this replica makes
     std::vector<DevDome> dome_recs;
@@ -299,6 +318,12 @@ int ensure_device(Scene& s, int device);                            // the scene
 // mrt_relight.hip: the texels of Scene::host_tex_stale and the DomeTables of host_dome_stale from
 // replica d (sync_host's part for texture updates; the caller has synchronised the device)
 int relight_read_back(Scene& s, DeviceState& d);
+// mrt_refit.hip: what a refit of replica d needs beyond the upload (the current device is d's);
+// after a rebuild (sched_stale) the height schedule alone, made again
+int refit_prepare(const Scene& s, DeviceState& d);
+// mrt_rebuild.hip: the world's topology, packets and boxes from replica d after a device
+// rebuild, in canonical numbers (sync_host's part; the caller has synchronised the device)
+int rebuild_read_back(Scene& s, DeviceState& d);
 
 }  // namespace mrt
 #endif   // __HIPCC__

@@ -24,51 +24,13 @@
 
 #include "mrt_device.h"
 #include "mrt_kernels.h"
+#include "mrt_refit_dev.h"
 
 namespace mrt {
 
 namespace {
 
 constexpr int kRefitWG = 256;
-
-struct DBox {
-    float lo[3], hi[3];
-};
-__device__ __forceinline__ DBox d_empty_box() {   // empty_box(): +-MIRO_TMAX
-    return DBox{{1e12f, 1e12f, 1e12f}, {-1e12f, -1e12f, -1e12f}};
-}
-__device__ __forceinline__ DBox d_merge(const DBox& a, const DBox& b) {
-    DBox r;
-    for (int k = 0; k < 3; k++) {
-        r.lo[k] = std_min(a.lo[k], b.lo[k]);
-        r.hi[k] = std_max(a.hi[k], b.hi[k]);
-    }
-    return r;
-}
-// slot k of a node (SoA: min xyz, max xyz, four slots each) as a box, and back
-__device__ __forceinline__ DBox d_slot_box(const QNode& q, int k) {
-    return DBox{{q.box[0 + k], q.box[4 + k], q.box[8 + k]}, {q.box[12 + k], q.box[16 + k], q.box[20 + k]}};
-}
-__device__ __forceinline__ void d_store_slot(QNode& q, int k, const DBox& b) {
-    q.box[0 + k] = b.lo[0]; q.box[4 + k] = b.lo[1]; q.box[8 + k] = b.lo[2];
-    q.box[12 + k] = b.hi[0]; q.box[16 + k] = b.hi[1]; q.box[20 + k] = b.hi[2];
-}
-// box i of the float4 pairs (min xyz, max xyz) in lbox and fixed, and back
-template <typename I>
-__device__ __forceinline__ DBox d_load_box(const float4* p, I i) {
-    const float4 lo = p[2 * i], hi = p[2 * i + 1];
-    return DBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
-}
-template <typename I>
-__device__ __forceinline__ void d_store_box(float4* p, I i, const DBox& b) {
-    p[2 * (size_t)i] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-    p[2 * (size_t)i + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
-}
-// Builder::box3 of a triangle's vertices
-__device__ __forceinline__ DBox d_tri_box(const float4 A, const float4 B, const float4 C) {
-    return DBox{{std_min(A.x, std_min(B.x, C.x)), std_min(A.y, std_min(B.y, C.y)), std_min(A.z, std_min(B.z, C.z))},
-                {std_max(A.x, std_max(B.x, C.x)), std_max(A.y, std_max(B.y, C.y)), std_max(A.z, std_max(B.z, C.z))}};
-}
 
 // n packed (x, y, z) -> float4 (x, y, z, w) at dst (and dst2: the time-1 copy of a static mesh)
 __global__ __launch_bounds__(kRefitWG) void refit_scatter_kernel(float4* __restrict__ dst, float4* __restrict__ dst2,
@@ -316,14 +278,37 @@ int height_schedule(const std::vector<QNode>& N, size_t n_leaves, const std::vec
     return MRT_OK;
 }
 
-// What the refit of replica d needs beyond the upload, made once (the topology never
-// changes while the replica lives): the node lists by height in device numbers, the packet
-// box scratch and the fixed boxes of ProxyObject / MBObject lanes.  The current device is d's.
-int prepare(const Scene& s, DeviceState& d) {
-    if (d.refit_ready) return MRT_OK;
+// The height schedules of replica d: the world's nodes by height, then each BLAS's (BLAS nodes
+// are not permuted), uploaded as refit_order (an earlier list is released: the caller has
+// synchronised the device if one was in use).
+int make_schedule(const Scene& s, DeviceState& d) {
     int rc;
-    std::vector<int32_t> order;   // the world's nodes by height, then each BLAS's
+    std::vector<int32_t> order;
     if ((rc = height_schedule(s.nodes, s.leaves.size(), d.node_perm, "the hierarchy", d.world, order))) return rc;
+    if (d.blas.size() != s.blas.size() || d.n_leaves_all < d.world.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    for (size_t b = 0; b < s.blas.size(); b++)
+        if ((rc = height_schedule(s.blas[b].nodes, s.blas[b].leaves.size(), {}, "a BLAS hierarchy", d.blas[b].tree, order))) return rc;
+    d.own.release(d.refit_order);
+    d.refit_order = nullptr;
+    if ((rc = d.own.upload(d.refit_order, order.data(), order.size() * sizeof(int32_t)))) return rc;
+    d.world.order = d.refit_order;   // each tree's part of the one list
+    const int32_t* at = d.refit_order + d.world.n_nodes;
+    for (DeviceState::BlasRange& R : d.blas) {
+        R.tree.order = at;
+        at += R.tree.n_nodes;
+    }
+    d.sched_stale = false;
+    return MRT_OK;
+}
+
+// What the refit of replica d needs beyond the upload, made once: the node lists by height in
+// device numbers (made again after a rebuild, which alone changes a topology while the replica
+// lives), the packet box scratch and the fixed boxes of ProxyObject / MBObject lanes.  The
+// current device is d's.
+int prepare(const Scene& s, DeviceState& d) {
+    if (d.refit_ready) return d.sched_stale ? make_schedule(s, d) : MRT_OK;
+    int rc;
+    if ((rc = make_schedule(s, d))) return rc;
     // fixed boxes: instance i at i, then the MBObject lanes
     std::vector<float4> fixed;
     auto push_box = [&](const float* b) {
@@ -344,29 +329,20 @@ int prepare(const Scene& s, DeviceState& d) {
     }
     std::vector<float> inst_m(16 * s.instances.size());   // m_transform: the device keeps inv / inv_t only
     for (size_t i = 0; i < s.instances.size(); i++) memcpy(&inst_m[16 * i], s.instances[i].m, 16 * sizeof(float));
-    // each BLAS: its nodes by height (BLAS nodes are not permuted) and the ids of its instances
-    if (d.blas.size() != s.blas.size() || d.n_leaves_all < d.world.n_leaves) { set_error("refit: replica out of date"); return MRT_ERR_INVALID; }
+    // each BLAS: the ids of its instances
     std::vector<int32_t> binsts;
     for (size_t b = 0; b < s.blas.size(); b++) {
         DeviceState::BlasRange& R = d.blas[b];
-        if ((rc = height_schedule(s.blas[b].nodes, s.blas[b].leaves.size(), {}, "a BLAS hierarchy", R.tree, order))) return rc;
         R.inst_at = (uint32_t)binsts.size();
         for (size_t i = 0; i < s.instances.size(); i++)
             if (s.instances[i].blas == (int32_t)b) binsts.push_back((int32_t)i);
         R.n_inst = (uint32_t)binsts.size() - R.inst_at;
     }
-    if ((rc = d.own.upload(d.refit_order, order.data(), order.size() * sizeof(int32_t))) ||
-        (rc = d.own.upload(d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4))) ||
+    if ((rc = d.own.upload(d.refit_fixed, fixed.data(), fixed.size() * sizeof(float4))) ||
         (rc = d.own.upload(d.refit_mbslot, mbslot.data(), mbslot.size() * sizeof(int32_t))) ||
         (rc = d.own.upload(d.refit_inst_m, inst_m.data(), inst_m.size() * sizeof(float))) ||
         (rc = d.own.upload(d.refit_blas_insts, binsts.data(), binsts.size() * sizeof(int32_t))))
         return rc;
-    d.world.order = d.refit_order;   // each tree's part of the one list
-    const int32_t* at = d.refit_order + d.world.n_nodes;
-    for (DeviceState::BlasRange& R : d.blas) {
-        R.tree.order = at;
-        at += R.tree.n_nodes;
-    }
     d.mesh_prim0.assign(s.meshes.size(), -1);   // first prim of each world mesh
     for (size_t o = s.obj_mesh.size(); o-- > 0;)
         if (s.obj_mesh[o] >= 0) d.mesh_prim0[(size_t)s.obj_mesh[o]] = (int32_t)o;
@@ -467,12 +443,20 @@ void mark_blas_stale(Scene& S, int32_t b) {
 // empty: the same) and the triangles of packets L (DLeaf AoS to the canonical SoA).
 int read_tree(const DeviceState& d, const RefitTree& T, const std::vector<int32_t>& perm, std::vector<QNode>& N,
               std::vector<QLeaf>& L) {
-    std::vector<QNode> DN(T.n_nodes);
+    // a rebuilt world tree (mrt_rebuild.hip) lies in the world's node range of the upload and in the tail past the image's nodes
+    const bool tail = &T == &d.world && d.rebuild_ready;
+    const size_t head = tail ? d.rb_world_nodes : T.n_nodes, extra = tail ? d.rb_extra : 0;
+    std::vector<QNode> DN(head + extra);
     std::vector<DLeaf> DL(T.n_leaves);
-    if (!DN.empty()) HIP_OK(hipMemcpy(DN.data(), d.nodes + T.node_base, DN.size() * sizeof(QNode), hipMemcpyDeviceToHost));
+    if (head) HIP_OK(hipMemcpy(DN.data(), d.nodes + T.node_base, head * sizeof(QNode), hipMemcpyDeviceToHost));
+    if (extra) HIP_OK(hipMemcpy(DN.data() + head, d.nodes + d.rb_tail, extra * sizeof(QNode), hipMemcpyDeviceToHost));
     if (!DL.empty()) HIP_OK(hipMemcpy(DL.data(), d.leaves + T.leaf_base, DL.size() * sizeof(DLeaf), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N.size() && i < DN.size(); i++)
-        memcpy(N[i].box, DN[perm.empty() ? i : (size_t)perm[i]].box, sizeof N[i].box);
+    for (size_t i = 0; i < N.size(); i++) {
+        size_t at = perm.empty() ? i : (size_t)perm[i];
+        if (at >= head) at = extra && at >= d.rb_tail ? head + (at - d.rb_tail) : DN.size();
+        if (at >= DN.size()) continue;
+        memcpy(N[i].box, DN[at].box, sizeof N[i].box);
+    }
     for (size_t i = 0; i < L.size() && i < DL.size(); i++)
         for (int k = 0; k < 4; k++)
             for (int c = 0; c < 9; c++) L[i].t[4 * c + k] = DL[i].tri[k][c];
@@ -486,6 +470,7 @@ int read_tree(const DeviceState& d, const RefitTree& T, const std::vector<int32_
 // boxes of the instances an async update left on the device, and from them the binning boxes
 // of every replica.
 int sync_host(Scene& s, bool meshes_only) {
+    if (s.host_topo_stale) meshes_only = false;   // after an async rebuild every refit needs the new topology first
     if (meshes_only ? s.host_mesh_stale.empty() && !s.host_inst_stale : !s.host_stale()) return MRT_OK;
     DeviceState* d = s.dev ? s.dev : (s.devs.empty() ? nullptr : s.devs[0]);
     if (!d) { set_error("refit: the device copy that is ahead of the host is gone"); return MRT_ERR_INVALID; }
@@ -494,7 +479,11 @@ int sync_host(Scene& s, bool meshes_only) {
     HIP_OK(hipSetDevice(d->device));
     HIP_OK(hipDeviceSynchronize());
     int rc;
-    if (s.host_bvh_stale && !meshes_only && (rc = read_tree(*d, d->world, d->node_perm, s.nodes, s.leaves))) return rc;
+    if (s.host_topo_stale) {   // a device rebuild: the topology, and with it the boxes and the triangles
+        if ((rc = rebuild_read_back(s, *d))) return rc;
+    } else if (s.host_bvh_stale && !meshes_only && (rc = read_tree(*d, d->world, d->node_perm, s.nodes, s.leaves))) {
+        return rc;
+    }
     if (!meshes_only && (rc = relight_read_back(s, *d))) return rc;   // texels and dome tables of a device texture update
     std::vector<float4> buf;
     auto read3 = [&](std::vector<v3>& dst, const float4* src) -> int {
@@ -636,6 +625,8 @@ int async_ready(Scene& S, const Mesh* M, const std::string& name) {
         return MRT_ERR_INVALID;
     }
     HIP_OK(hipSetDevice(S.dev->device));
+    if (S.host_topo_stale)   // an async rebuild: the schedule needs the topology it left on the device
+        if (const int rc = sync_host(S)) return rc;
     return prepare(S, *S.dev);
 }
 
@@ -657,6 +648,9 @@ int mesh_async(Scene& S, int mesh, int kind, const std::string& name, const floa
 }
 
 }  // namespace
+
+int refit_prepare(const Scene& s, DeviceState& d) { return prepare(s, d); }
+
 }  // namespace mrt
 
 using namespace mrt;

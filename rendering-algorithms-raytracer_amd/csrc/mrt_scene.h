@@ -120,6 +120,10 @@ struct Scene {
     // After mrt_scene_update_instances_async the matrices, inverses and boxes of `instances`
     // are behind the replica's too (host_inst_stale).
     bool host_bvh_stale = false;
+    // After mrt_scene_rebuild_bvh_async the world's node count, child words and packets are
+    // behind the replica's as well (the synchronous form reads them back itself): sync_host
+    // renumbers them breadth first and every replica's refit schedule is made again.
+    bool host_topo_stale = false;
     std::vector<int32_t> host_mesh_stale;
     bool host_inst_stale = false;
     // After mrt_scene_deform_mesh on an uploaded scene the nodes and leaves of these BLASes
@@ -167,6 +171,12 @@ void refit_blas_host(Scene& s, int32_t b);
 // The box the build gave world object o when it is a ProxyObject or an MBObject lane
 // (Builder::tri_aabb): min xyz, max xyz.  False for a plain triangle.
 bool fixed_lane_box(const Scene& s, int32_t o, float box[6]);
+// mrt_scene_rebuild_bvh on the host: a new topology for the world hierarchy from the lanes its
+// packets hold now (mrt_rebuild.hip's kernels apply the same rule); every
+// replica is re-uploaded on its next use.
+void rebuild_host(Scene& s);
+// mrt_scene_bvh_cost over the canonical arrays (the caller has run sync_host)
+double bvh_cost_host(const Scene& s);
 // mrt_refit.hip: bring a stale host copy up to date from the device (synchronises); a
 // no-op when nothing is stale
 // (meshes_only: the vertices and normals, and the instances, an async update left there, not

@@ -761,8 +761,14 @@ class Scene:
                                       lp.ctypes.data_as(C.POINTER(C.c_int32))), "blas_export")
         return nb, nc, lt, lp
 
+    def _refresh_bvh_info(self):
+        info = _lib.mrt_bvh_info()
+        check(lib().mrt_scene_bvh_info(self.handle, C.byref(info)), "bvh_info")
+        self.bvh_info = {k: getattr(info, k) for k, _ in info._fields_}
+        return self.bvh_info
+
     def bvh_export(self):
-        info = self.bvh_info
+        info = self._refresh_bvh_info()   # a rebuild changes the counts
         nb = np.zeros((info["nodes"], 24), np.float32)
         nc = np.zeros((info["nodes"], 4), np.int32)
         lt = np.zeros((info["leaves"], 36), np.float32)
@@ -988,6 +994,33 @@ class Scene:
         check(L.mrt_scene_update_instances(self.handle, idv.ctypes.data if idv is not None else None, n, m.ctypes.data,
                                            C.byref(ms)), "updateInstances")
         return float(ms.value)
+
+    def rebuildBVH(self, stream=None):
+        """A new topology for the world hierarchy from the lanes its packets hold now, on the
+        device and without a re-upload (mrt_scene_rebuild_bvh): where Scene::preCalc builds again
+        after geometry has moved.  The tree is a Morton tree: measured faster than a refitted tree
+        where instances have changed places, slower where one mesh of large triangles deforms
+        (DESIGN.md 6i); bvhCost() and a timed frame decide.  Without a
+        `stream` the synchronous entry acts on every replica and returns the device time in ms
+        (0.0 for a scene not yet uploaded: the host rebuilds by the same rule); with a torch
+        stream, mrt_scene_rebuild_bvh_async on it and None: no synchronisation, except that the
+        first rebuild of a replica allocates and waits for the device once if its node array grows."""
+        L = lib()
+        if stream is not None:
+            check(L.mrt_scene_upload(self.handle, self.device), "upload")
+            check(L.mrt_scene_rebuild_bvh_async(self.handle, self._stream_arg(stream)), "rebuildBVH")
+            return None
+        ms = C.c_float(0.0)
+        check(L.mrt_scene_rebuild_bvh(self.handle, C.byref(ms)), "rebuildBVH")
+        self._refresh_bvh_info()
+        return float(ms.value)
+
+    def bvhCost(self):
+        """The surface-area measure of the world hierarchy (mrt_scene_bvh_cost): every used slot's
+        box area over the root box's, a leaf slot once per lane of its packet."""
+        cost = C.c_double(0.0)
+        check(lib().mrt_scene_bvh_cost(self.handle, C.byref(cost)), "bvhCost")
+        return float(cost.value)
 
     def instance_count(self):
         return check(lib().mrt_scene_instance_count(self.handle), "instance_count")

@@ -39,6 +39,7 @@ EXPORTS = [
     "mrt_scene_update_lights", "mrt_scene_update_lights_async", "mrt_scene_update_material",
     "mrt_scene_update_material_async", "mrt_scene_update_texture", "mrt_scene_update_texture_async",
     "mrt_scene_texture_update_status", "mrt_scene_dome_export_derived", "mrt_scene_upload_count",
+    "mrt_scene_rebuild_bvh", "mrt_scene_rebuild_bvh_async", "mrt_scene_bvh_cost",
 ]
 
 
@@ -251,6 +252,10 @@ def load():
         L.mrt_scene_texture_update_status.argtypes = [vp, _ip]
         L.mrt_scene_dome_export_derived.argtypes = [vp, C.c_int32, _fp, _ip, _ip]
         L.mrt_scene_upload_count.argtypes = [vp]
+    if hasattr(L, "mrt_scene_rebuild_bvh"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_scene_rebuild_bvh.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.mrt_scene_rebuild_bvh_async.argtypes = [C.c_void_p, C.c_void_p]
+        L.mrt_scene_bvh_cost.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mrt_scene_last_stats.argtypes = [C.c_void_p, C.POINTER(mrt_stats)]
     L.mrt_set_tuning.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "mrt_get_tuning"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
