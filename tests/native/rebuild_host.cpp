@@ -1,5 +1,6 @@
 // rebuild_host (csrc/host_build.cpp: mrt_scene_rebuild_bvh on the host) on the fixtures of
-// tests/test_rebuild.py, without a GPU and without Python: built against host_build.cpp,
+// tests/test_rebuild.py and three of tests/test_rebuild_shapes.py (a line at P = 513, a cloud at
+// P = 1025, the key cell edges), without a GPU and without Python: built against host_build.cpp,
 // host_texture.cpp and host_image.cpp with -fsanitize=address,undefined
 // (tests/test_rebuild_native.py), so an index out of range or a read of freed memory ends the
 // program.  After every rebuild (two per scene) the tree's own invariants are checked: every
@@ -221,6 +222,54 @@ int main(int argc, char** argv) {
         }
         add_soup(s, t);
         run("256 triangles on a line", s, 63);
+    }
+    {   // the same at P = 513: 512 binary nodes, two levels of the segment tree at and below node 256
+        Scene s;
+        base_scene(s);
+        std::vector<float> t;
+        for (int i = 0; i < 2052; i++) {
+            const float x = (float)i * 0.0625f;
+            for (float v : {x, 0.f, 0.f, x + 0.05f, 0.f, 0.f, x, 0.05f, 0.01f}) t.push_back(v);
+        }
+        add_soup(s, t);
+        run("2052 triangles on a line", s, 512);
+    }
+    {   // P = 1025: small triangles in a cube, nodes of two, three and four children
+        Scene s;
+        base_scene(s);
+        std::vector<float> t;
+        uint32_t x = 4097u;
+        auto next = [&x]() {
+            x = x * 1664525u + 1013904223u;
+            return (float)(x >> 8) / 16777216.f;
+        };
+        for (int i = 0; i < 4097; i++) {
+            const float c[3] = {next() * 6.f - 3.f, next() * 6.f - 3.f, next() * 6.f - 3.f};
+            for (int v = 0; v < 3; v++)
+                for (int a = 0; a < 3; a++) t.push_back(c[a] + next() * 0.1f - 0.05f);
+        }
+        add_soup(s, t);
+        run("cloud of 4097 triangles", s);
+    }
+    {   // key cell edges: a triangle that spans the root box, and point triangles on, and one and two
+        // floats to either side of, the edges of cells 0 .. 3, 511 .. 513 and 1022 .. 1024 of each axis
+        Scene s;
+        base_scene(s);
+        const float lo[3] = {-1.f, 10.f, -0.3f}, hi[3] = {2.f, 10.7f, 0.9f};
+        std::vector<float> t = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], lo[0], hi[1], lo[2]};
+        for (int a = 0; a < 3; a++)
+            for (int k : {0, 1, 2, 3, 511, 512, 513, 1022, 1023, 1024}) {
+                float v = (float)((double)lo[a] + ((double)hi[a] - (double)lo[a]) * k / 1024.0);
+                v = nextafterf(nextafterf(v, -INFINITY), -INFINITY);
+                for (int j = 0; j < 5; j++, v = nextafterf(v, INFINITY)) {
+                    float p[3] = {(float)(((double)lo[0] + hi[0]) / 2), (float)(((double)lo[1] + hi[1]) / 2),
+                                  (float)(((double)lo[2] + hi[2]) / 2)};
+                    p[a] = fminf(fmaxf(v, lo[a]), hi[a]);
+                    for (int c = 0; c < 3; c++) t.insert(t.end(), {p[0], p[1], p[2]});
+                }
+            }
+        add_soup(s, t);
+        run("cell edges", s);
     }
     {   // no extent in y
         Scene s;

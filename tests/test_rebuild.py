@@ -225,13 +225,16 @@ TEAPOT_CAM = dict(eye=(0.2, 2.2, 4.6), lookAt=(0.1, 0.9, 0), up=(0, 1, 0), fov=4
 class Kinds:
     """All four lane kinds at once: a plain mesh (a small stand-in sphere, mesh 0), an
     alpha-mapped mesh (mesh 1), the three instances PLACED3 of a small sphere (mesh 2), a motion-blurred
-    sphere (mesh 3) and a floor (mesh 4).  line: the 256 triangles of line_tris as mesh 0
-    instead, whose rebuilt tree needs more nodes than the built one has."""
+    sphere (mesh 3) and a floor (mesh 4).  line: the triangles of line_tris as mesh 0 instead
+    (True: 256 of them, or their number), whose rebuilt tree needs more nodes than the built one
+    has.  lights: the scene's lights in place of the point light.  cutout: the alpha map is an
+    RGBA checkerboard of 2 x 2 texels whose alpha channel cuts every other square out, and the
+    instanced sphere has that material too (alpha lanes inside an instance)."""
 
-    def __init__(self, mats=PLACED3, line=False, mb=None, plain=None):
+    def __init__(self, mats=PLACED3, line=False, mb=None, plain=None, lights=None, cutout=False):
         P = self.P = miro.Scene()
         if line:
-            V, N, F = line_tris()
+            V, N, F = line_tris(256 if line is True else int(line))
             V = np.asarray(V * F32(0.5) + np.array([-4.0, 2.0, 0.0], F32), F32)
         else:
             V, F, N = scenes.bunny_standin(10, 5)
@@ -247,11 +250,19 @@ class Kinds:
         am.setTexCoords(np.array([[0, 0], [1, 0], [1, 1], [0, 1]], F32), aF)
         alpha = miro.Lambert((0.9, 0.9, 0.2))
         tex = np.asarray((np.indices((8, 8)).sum(0) % 2)[..., None], F32)   # a checkerboard, one channel
-        alpha.setAlphaMap(miro.Texture(miro.RawImage(8, 8, tex, miro.TEX_GRAY)))
+        if cutout:
+            rgba = np.ones((8, 8, 4), F32)
+            rgba[..., 3] = (np.indices((8, 8)) // 2).sum(0) % 2
+            alpha.setAlphaMap(miro.Texture(miro.RawImage(8, 8, rgba, miro.TEX_RGBA)))
+        else:
+            alpha.setAlphaMap(miro.Texture(miro.RawImage(8, 8, tex, miro.TEX_GRAY)))
         miro.makeMeshObjs(P, am, alpha)
         self.bV, self.bN, self.bF = blas_mesh()
         objs, bvh = miro.Objects(), miro.BVH()
-        miro.ProxyObject.setupProxy(tri_mesh(self.bV, self.bN, self.bF), miro.Lambert((0.3, 0.8, 0.4)), objs, bvh)
+        bm = tri_mesh(self.bV, self.bN, self.bF)
+        if cutout:   # the checkerboard once across the sphere (x in [-0.6, 0.6], y in [0.05, 1.25])
+            bm.setTexCoords(np.asarray((self.bV[:, :2] + F32(0.6)) / F32(1.25), F32), self.bF)
+        miro.ProxyObject.setupProxy(bm, alpha if cutout else miro.Lambert((0.3, 0.8, 0.4)), objs, bvh)
         self.mats = list(mats)
         for M in self.mats:
             P.addObject(miro.ProxyObject(objs, bvh, miro.Matrix4x4(M)))
@@ -260,7 +271,8 @@ class Kinds:
         miro.makeMBMeshObjs(P, tri_mesh(self.mV, self.bN, self.bF), tri_mesh(self.mV2, self.bN, self.bF), miro.Lambert((0.9, 0.4, 0.3)))
         fl = floor_mesh()
         miro.makeMeshObjs(P, fl, miro.Lambert((0.6, 0.6, 0.6)))
-        P.addLight(point_light())
+        for l in ([point_light()] if lights is None else lights):
+            P.addLight(l)
         P.setBGColor((0.1, 0.1, 0.3))
         P.preCalc()
         self.inst0 = len(F) + len(aF)           # the proxies' world prims
@@ -276,8 +288,8 @@ class Kinds:
             e[3] = (mV, self.bF)
         return prim_verts_of(*e)
 
-    def fixed(self, mats=None, mb=None):
-        root = self.P.blas_export(0)[0][0]
+    def fixed(self, mats=None, mb=None, root=None):
+        root = self.P.blas_export(0)[0][0] if root is None else root
         out = {self.inst0 + i: instance_box(root, M) for i, M in enumerate(mats or self.mats)}
         mV, mV2 = mb if mb is not None else (self.mV, self.mV2)
         for t, f in enumerate(self.bF):
@@ -323,9 +335,17 @@ def _line_kinds():
     return S.P, S.pv(), S.fixed()
 
 
+def _line_1028_kinds():
+    """The tail fixture with a BLAS at more than one workgroup of packets: P = 275, and the BLAS's
+    nodes lie between the world's node range and the tail the rebuild adds."""
+    S = Kinds(line=1028)
+    return S.P, S.pv(), S.fixed()
+
+
 FIXTURES = {"one_triangle": _one, "five_triangles": _five, "teapot": teapot_scene, "identical_70": _identical,
-            "line_256": _line, "flat": _flat, "four_kinds": _kinds}
+            "line_256": _line, "flat": _flat, "four_kinds": _kinds, "line_1028_and_instances": _line_1028_kinds}
 GPU_FIXTURES = dict(FIXTURES, line_and_instances=_line_kinds)
+TAIL_FIXTURES = ("line_256", "line_and_instances", "line_1028_and_instances")   # M passes the built tree's node count
 
 
 def assert_tree(export, n_prims, pv, fixed):
@@ -385,6 +405,9 @@ def test_host_rebuild_is_the_restatement(name):
     if name == "line_256":   # every node is binary, and the tree outgrows the built one's node range
         assert len(ex1[1]) == 63 == len(ex1[3]) - 1 and ((ex1[1] != EMPTY).sum(1) == 2).all()
         assert len(ex1[1]) > built_nodes
+    if name == "line_1028_and_instances":   # the premise: more than one workgroup of packets, a tail, a BLAS before it
+        assert (n, len(ex1[3]), len(ex1[1]), built_nodes) == (1098, 275, 272, 179)
+        assert P.instance_count() == 3 and P.blas_export(0)[1].shape[0] > 0
     if name == "identical_70":   # equal codes: the order is the positions'
         order = [4 * li + k for li in range(len(ex0[3])) for k in range(4) if ex0[3][li, k] >= 0]
         assert ex1[3].ravel()[:70].tolist() == [int(ex0[3].ravel()[p]) for p in sorted(order)]
@@ -499,7 +522,7 @@ def cam_of(name):
         return TEAPOT_CAM
     if name == "four_kinds":
         return CAM
-    if name == "line_and_instances":   # the first instance fills a third of the view
+    if name in ("line_and_instances", "line_1028_and_instances"):   # the first instance fills a third of the view
         return dict(eye=(-4.5, 1.2, 5.0), lookAt=(-4.5, 0.8, 1.5), up=(0, 1, 0), fov=45)
     if name in ("line_256",):
         return dict(eye=(8.0, 0.02, 1.5), lookAt=(8, 0.02, 0), up=(0, 1, 0), fov=60)   # a pixel is half a triangle wide
@@ -552,7 +575,7 @@ def test_device_rebuild_is_the_restatement(name):
     assert_arrays(ex1, want)
     assert A.bvh_info["nodes"] == len(want[1]) and A.bvh_info["leaves"] == len(want[3])
     assert_tree(ex1, n, pv, fixed)
-    if name in ("line_256", "line_and_instances"):
+    if name in TAIL_FIXTURES:
         assert len(want[1]) > built   # the grown node array
     assert A.bvhCost() == pytest.approx(cost_of(want), rel=1e-12)
     B, _, _ = GPU_FIXTURES[name]()
@@ -560,7 +583,7 @@ def test_device_rebuild_is_the_restatement(name):
     fa, fb = counted(A, cam), counted(B, cam)
     assert_counted(fa, fb)
     assert (fa["hits"]["prim"] >= 0).sum() > 20   # the scene is in view
-    if name == "line_and_instances":
+    if name in ("line_and_instances", "line_1028_and_instances"):
         assert (fa["hits"]["prim"] >= n).sum() > 50   # and so are its instances, as before
         assert np.array_equal(fa["hits"]["prim"] >= n, f0["hits"]["prim"] >= n)
     assert_queries(queries(A, cam), queries(B, cam))

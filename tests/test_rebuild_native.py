@@ -1,7 +1,8 @@
 """rebuild_host (csrc/host_build.cpp: mrt_scene_rebuild_bvh on the host) under the address and
 undefined-behaviour sanitizers, without a GPU and without Python in the process:
 tests/native/rebuild_host.cpp, built with g++ against the plain C++ host sources, rebuilds the
-fixtures of tests/test_rebuild.py twice each and checks the tree's invariants."""
+fixtures of tests/test_rebuild.py, and a line at P = 513, a cloud at P = 1025 and the key cell
+edges of tests/test_rebuild_shapes.py, twice each and checks the tree's invariants."""
 import os
 import shutil
 import subprocess
@@ -25,3 +26,7 @@ def test_rebuild_host_under_sanitizers(tmp_path):
     r = subprocess.run([exe, os.path.join(HERE, "golden", "models")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "256 triangles on a line: 256 prims" in r.stdout and "four lane kinds" in r.stdout
+    # the sizes and key values of tests/test_rebuild_shapes.py: P = 513 all binary, P = 1025, P = 38
+    assert "2052 triangles on a line: 2052 prims" in r.stdout and "rebuilt 512 nodes" in r.stdout
+    assert "cloud of 4097 triangles: 4097 prims" in r.stdout and "1025 packets" in r.stdout
+    assert "cell edges: 151 prims" in r.stdout and "38 packets" in r.stdout
