@@ -866,6 +866,47 @@ int mrt_device_wall_clock_khz(const mrt_scene* s);
  * restated, csrc/mrt_libm.h), or its rcp_nr(x) (fn 2: the RCPSS emulation and Newton step
  * of every triangle test; y unused). */
 int mrt_debug_libm(int fn, const float* x, const float* y, size_t n, float* out);
+/* Ray-binning probe: the three launches of csrc/mrt_bin.hip (keys + per-block counts, the
+ * scan of the bins, the scatter) on host arrays, without a scene: every field of the
+ * renderer's own binning call comes from the caller.  items = n, or with has_n_dev
+ * min(n, min(cap1, n_dev * mul1 - sub) * mul2); slot i < items is valid iff nrays is null
+ * or i % m < nrays[i / m].  The key of a valid slot: direction cell (dbits per axis, major)
+ * and Morton code of the origin's cell (o - lo) * inv (obits per axis, minor); with hits
+ * (dbits = obits = 2) a slot whose pixel's hit id (the bits of hits[4 * (i / m) + 3]) is at
+ * or above n_world gets 1 << 11 | inst_class << 4 | direction cell of the last instance
+ * whose hit_base is at or below it, or with inst_cell 1 << 11 | BLAS bit << 10 | Morton code
+ * of its object-space cell << 4 | direction cell.  On return keys[i], i < items, holds the
+ * key or 0xFFFF (invalid slot), hist[b], b < 2^bits, the number of valid slots with key <=
+ * b, hist[2^bits] their total and perm[0 .. total) the valid slots in key order (bits: 12
+ * with hits, else 2 dbits + 3 obits).  keys and perm are copied to the device before the
+ * launches, so what they held past items / past total comes back as it was.
+ * Refused (MRT_ERR_INVALID, before any device call): a null probe, o, d, keys, hist or perm,
+ * m < 1, grid outside 1..1024, n at or above 2^31, inst_cell without inst_inv, hits
+ * without hit_base / inst_class, an inst_class value above 127; the binning's own refusals
+ * (key widths, instance tables) are returned as they are. */
+typedef struct mrt_bin_probe {
+    const float* o;             /* n x 4 floats: ray origins (w unused) */
+    const float* d;             /* n x 4 floats: ray directions */
+    uint32_t n;
+    int32_t has_n_dev;          /* 1: n_dev is placed on the device as the batch's count */
+    uint32_t n_dev;
+    uint32_t mul1, sub, cap1, mul2;
+    const uint8_t* nrays;       /* ceil(n / m) ray counts, or null */
+    uint32_t m;
+    float lo[3], inv[3];
+    int32_t dbits, obits;
+    int32_t grid;               /* workgroups of the count and scatter passes */
+    const float* hits;          /* ceil(n / m) x 4 floats (t, a, b, hit id bits), or null */
+    const int32_t* hit_base;    /* n_inst, ascending */
+    const uint16_t* inst_class; /* n_inst, each 0..127 */
+    int32_t n_inst, n_world;
+    const float* inst_cell;     /* 2 n_inst x 4 floats, or null */
+    const float* inst_inv;      /* n_inst x 12 floats: world-to-object matrices, 3 rows of 4 */
+    uint16_t* keys;             /* n, in / out */
+    uint32_t* hist;             /* 4097 words, out: the first 2^bits + 1 are written */
+    uint32_t* perm;             /* n, in / out */
+} mrt_bin_probe;
+int mrt_debug_bin_rays(const mrt_bin_probe* p);
 /* Ownership probe: the device allocations, pinned allocations, events and streams the library's
  * replicas, stream contexts and staging buffers hold in this process now.  It returns to its
  * earlier value when what was created since has been destroyed (mrt_scene_destroy). */

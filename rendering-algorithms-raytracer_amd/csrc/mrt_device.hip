@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mrt_bin.h"
@@ -2333,6 +2334,66 @@ int mrt_debug_libm(int fn, const float* x, const float* y, size_t n, float* out)
     hipLaunchKernelGGL(libm_kernel, dim3(blocks), dim3(256), 0, 0, fn, dx, dy, n, dout, dt);
     HIP_OK(hipGetLastError());
     return st.back(out, dout, b);
+}
+
+// bin_rays (mrt_bin.hip) as the renderer calls it, on the caller's arrays: no kernel of its own
+int mrt_debug_bin_rays(const mrt_bin_probe* p) {
+    const auto refuse = [](const char* m) { set_error(m); return MRT_ERR_INVALID; };
+    if (!p || !p->o || !p->d || !p->keys || !p->hist || !p->perm) return refuse("null ray-bin probe array");
+    if (p->m < 1) return refuse("ray-bin probe: m must be at least 1");
+    if (p->grid < 1 || p->grid > 1024) return refuse("ray-bin probe: grid must be 1..1024");
+    if (p->n >= 0x80000000u) return refuse("ray-bin probe: fewer than 2^31 rays");
+    if (p->inst_cell && !p->inst_inv) return refuse("ray-bin probe: inst_cell needs the instance matrices");
+    if (p->hits && (!p->hit_base || !p->inst_class || p->n_inst < 1)) return refuse("ray-bin probe: hits need the instance tables");
+    if (p->hits)   // (a larger class would carry the key past the bins)
+        for (int32_t i = 0; i < p->n_inst; i++)
+            if (p->inst_class[i] > 127) return refuse("ray-bin probe: inst_class above 127");
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_error("no HIP device"); return MRT_ERR_NO_DEVICE; }
+    const size_t n = p->n, px = (n + p->m - 1) / p->m, ni = p->hits ? (size_t)p->n_inst : 0;
+    Staged st;
+    // an empty array takes one element and no copy
+    const auto in = [&](const auto* host, size_t count) {
+        return count ? st.in(host, count * sizeof *host) : st.out<std::remove_cv_t<std::remove_pointer_t<decltype(host)>>>(sizeof *host);
+    };
+    BinArgs A{};
+    A.o = (const float4*)in(p->o, 4 * n);
+    A.d = (const float4*)in(p->d, 4 * n);
+    A.n = p->n;
+    A.n_dev = p->has_n_dev ? in(&p->n_dev, 1) : nullptr;
+    A.mul1 = p->mul1; A.sub = p->sub; A.cap1 = p->cap1; A.mul2 = p->mul2;
+    A.nrays = p->nrays ? in(p->nrays, px) : nullptr;
+    A.m = p->m;
+    for (int a = 0; a < 3; a++) { A.lo[a] = p->lo[a]; A.inv[a] = p->inv[a]; }
+    A.dbits = p->dbits; A.obits = p->obits;
+    std::vector<DevInstance> DI;
+    if (p->hits) {
+        A.hits = (const float4*)in(p->hits, 4 * px);
+        A.hit_base = in(p->hit_base, ni);
+        A.inst_class = in(p->inst_class, ni);
+        A.n_inst = p->n_inst; A.n_world = p->n_world;
+        if (p->inst_cell) {
+            DI.resize(ni);
+            for (size_t i = 0; i < ni; i++) {
+                memset(&DI[i], 0, sizeof(DevInstance));
+                memcpy(DI[i].inv, p->inst_inv + 12 * i, 12 * sizeof(float));
+                DI[i].inv[15] = 1.f;
+            }
+            A.inst_cell = (const float4*)in(p->inst_cell, 8 * ni);
+            A.insts = in(DI.data(), ni);
+        }
+    }
+    A.keys = const_cast<uint16_t*>(in((const uint16_t*)p->keys, n));
+    A.perm = const_cast<uint32_t*>(in((const uint32_t*)p->perm, n));
+    A.hist = st.out<uint32_t>(kBinHist * sizeof(uint32_t));
+    if (st.rc) return st.rc;
+    if (const int rc = bin_rays(A, p->grid, 0)) return rc;
+    HIP_OK(hipStreamSynchronize(0));
+    const int bits = A.hits ? kBinBits : 2 * A.dbits + 3 * A.obits;
+    int rc = st.back(p->hist, A.hist, ((size_t(1) << bits) + 1) * sizeof(uint32_t));
+    if (!rc && n) rc = st.back(p->keys, A.keys, n * sizeof(uint16_t));
+    if (!rc && n) rc = st.back(p->perm, A.perm, n * sizeof(uint32_t));
+    return rc;
 }
 
 }  // extern "C"

@@ -59,6 +59,49 @@ def debug_libm(fn: str, x, y=None):
     return out
 
 
+def bin_rays(o, d, *, n_dev=None, mul1=1, sub=0, cap1=0xFFFFFFFF, mul2=1, nrays=None, m=1, lo=(0, 0, 0), inv=(1, 1, 1),
+             dbits=2, obits=2, grid=1, hits=None, hit_base=None, inst_class=None, n_world=0, inst_cell=None,
+             inst_inv=None, keys_fill=0xABCD, perm_fill=0xDEADBEEF):
+    """The ray-binning launches (csrc/mrt_bin.hip) on host arrays (mrt_debug_bin_rays, include/mrt.h):
+    o, d (n, 4) floats; the count, validity, key and instance-table fields as the C entry takes them.
+    Returns {"keys": (n,) uint16, "hist": (2^bits + 1,) uint32, "perm": (n,) uint32, "bits"}; keys and
+    perm enter the launches filled with keys_fill / perm_fill, so words left alone keep them."""
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 4)
+    d = np.ascontiguousarray(d, np.float32).reshape(-1, 4)
+    n = len(o)
+    assert len(d) == n
+    keep = [o, d]   # the arrays the probe points into
+
+    def arr(a, dtype, count=None):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype).reshape(-1)
+        assert count is None or m < 1 or a.size == count, (a.size, count)   # (m < 1: the entry refuses it)
+        keep.append(a)
+        return a.ctypes.data
+
+    px = (n + m - 1) // m if m >= 1 else 0
+    n_inst = 0 if hit_base is None else int(np.size(hit_base))
+    P = _lib.mrt_bin_probe()
+    P.o, P.d, P.n = o.ctypes.data, d.ctypes.data, n
+    P.has_n_dev, P.n_dev = int(n_dev is not None), int(n_dev or 0)
+    P.mul1, P.sub, P.cap1, P.mul2 = int(mul1), int(sub), int(cap1), int(mul2)
+    P.nrays, P.m = arr(nrays, np.uint8, px), int(m)
+    P.lo, P.inv = f3(lo), f3(inv)
+    P.dbits, P.obits, P.grid = int(dbits), int(obits), int(grid)
+    P.hits = arr(hits, np.float32, 4 * px)
+    P.hit_base, P.inst_class = arr(hit_base, np.int32), arr(inst_class, np.uint16, n_inst if hit_base is not None else None)
+    P.n_inst, P.n_world = n_inst, int(n_world)
+    P.inst_cell, P.inst_inv = arr(inst_cell, np.float32, 8 * n_inst), arr(inst_inv, np.float32, 12 * n_inst)
+    keys = np.full(max(n, 1), keys_fill, np.uint16)
+    perm = np.full(max(n, 1), perm_fill, np.uint32)
+    hist = np.full(4097, 0xFFFFFFFF, np.uint32)
+    P.keys, P.hist, P.perm = keys.ctypes.data, hist.ctypes.data, perm.ctypes.data
+    check(lib().mrt_debug_bin_rays(C.byref(P)), "mrt_debug_bin_rays")
+    bits = 12 if hits is not None else 2 * int(dbits) + 3 * int(obits)
+    return {"keys": keys[:n], "hist": hist[:(1 << bits) + 1], "perm": perm[:n], "bits": bits}
+
+
 class Vector3(tuple):
     """Plain 3-tuple with the reference's constructors: Vector3(s) or Vector3(x, y, z)."""
 

@@ -39,7 +39,7 @@ EXPORTS = [
     "mrt_scene_update_lights", "mrt_scene_update_lights_async", "mrt_scene_update_material",
     "mrt_scene_update_material_async", "mrt_scene_update_texture", "mrt_scene_update_texture_async",
     "mrt_scene_texture_update_status", "mrt_scene_dome_export_derived", "mrt_scene_upload_count",
-    "mrt_scene_rebuild_bvh", "mrt_scene_rebuild_bvh_async", "mrt_scene_bvh_cost",
+    "mrt_scene_rebuild_bvh", "mrt_scene_rebuild_bvh_async", "mrt_scene_bvh_cost", "mrt_debug_bin_rays",
 ]
 
 
@@ -104,6 +104,16 @@ class mrt_stats(C.Structure):
                 ("secondary_rays", C.c_uint64), ("shadow_wave_steps", C.c_uint64), ("shadow_node_visits", C.c_uint64),
                 ("fused", C.c_int32), ("chain", C.c_int32), ("chain_budget_bytes", C.c_uint64),
                 ("chain_chunks", C.c_uint32), ("chain_fallbacks", C.c_int32)]
+
+
+class mrt_bin_probe(C.Structure):
+    _fields_ = [("o", C.c_void_p), ("d", C.c_void_p), ("n", C.c_uint32), ("has_n_dev", C.c_int32), ("n_dev", C.c_uint32),
+                ("mul1", C.c_uint32), ("sub", C.c_uint32), ("cap1", C.c_uint32), ("mul2", C.c_uint32),
+                ("nrays", C.c_void_p), ("m", C.c_uint32), ("lo", C.c_float * 3), ("inv", C.c_float * 3),
+                ("dbits", C.c_int32), ("obits", C.c_int32), ("grid", C.c_int32), ("hits", C.c_void_p),
+                ("hit_base", C.c_void_p), ("inst_class", C.c_void_p), ("n_inst", C.c_int32), ("n_world", C.c_int32),
+                ("inst_cell", C.c_void_p), ("inst_inv", C.c_void_p), ("keys", C.c_void_p), ("hist", C.c_void_p),
+                ("perm", C.c_void_p)]
 
 
 _fp = C.POINTER(C.c_float)
@@ -286,6 +296,8 @@ def load():
         L.mrt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if hasattr(L, "mrt_debug_libm"):   # (absent from round-4 builds loaded for A/B runs via MRT_LIB)
         L.mrt_debug_libm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    if hasattr(L, "mrt_debug_bin_rays"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
+        L.mrt_debug_bin_rays.argtypes = [C.POINTER(mrt_bin_probe)]
     if hasattr(L, "mrt_debug_live_resources"):   # (absent from earlier builds loaded for A/B runs via MRT_LIB)
         L.mrt_debug_live_resources.argtypes = []
         L.mrt_debug_live_resources.restype = C.c_int64

@@ -1,12 +1,14 @@
 // The host image of a device replica (build_image, csrc/host_image.cpp) on three scenes, without
-// a GPU: the invariants every kernel relies on, and the byte total mrt_scene_info.device_bytes
-// reports.  Built against host_build.cpp, host_texture.cpp and host_image.cpp
+// a GPU: the invariants every kernel relies on, the instance-major ray-bin tables (csrc/mrt_bin.h),
+// and the byte total mrt_scene_info.device_bytes reports.  Built against host_build.cpp, host_texture.cpp and host_image.cpp
 // (tests/test_device_image.py).
 //   device_image <models dir> <bytes cornell> <bytes instanced> <bytes motion>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -126,6 +128,74 @@ static void check_image(const Scene& s, const DeviceImage& g, size_t want_bytes)
     CHECK(g.bytes == want_bytes, "device bytes %zu, recorded %zu", g.bytes, want_bytes);
 }
 
+// The box of BLAS b from its own leaf packets in the image: the corners A, A + e0, A + e1 of every
+// triangle.  *tol: what a corner rebuilt from the stored edges may differ from the vertex the
+// build boxed: e = fl(B - A) and fl(A + e) round once each, at most an ulp of the largest
+// coordinate together; 4 ulps are allowed.
+static void blas_box(const DeviceImage& g, size_t b, float lo[3], float hi[3], float* tol) {
+    const RefitTree& T = g.blas[b].tree;
+    bool any = false;
+    float big = 0.f;
+    for (uint32_t p = T.leaf_base; p < T.leaf_base + T.n_leaves; p++)
+        for (int j = 0; j < 4; j++) {
+            const DLeaf& L = g.DL[p];
+            if (L.prim[j] < 0) continue;
+            for (int c = 0; c < 3; c++)
+                for (int a = 0; a < 3; a++) {
+                    const float x = c ? L.tri[j][a] + L.tri[j][3 * c + a] : L.tri[j][a];
+                    lo[a] = any ? std::min(lo[a], x) : x;
+                    hi[a] = any ? std::max(hi[a], x) : x;
+                    big = std::max(big, fabsf(x));
+                }
+            any = true;
+        }
+    *tol = 4.f * 1.1920929e-7f * big;
+}
+
+// The instance-major ray-bin tables (csrc/mrt_bin.h): hit bases, classes, object-space cells
+static void check_bin_tables(const Scene& s, const DeviceImage& g) {
+    const size_t ni = g.DI.size();
+    CHECK(g.hit_base.size() == ni && g.cls.size() == ni && g.cell.size() == 2 * ni, "table sizes %zu %zu %zu of %zu instances",
+          g.hit_base.size(), g.cls.size(), g.cell.size(), ni);
+    if (g.hit_base.size() != ni || g.cls.size() != ni || g.cell.size() != 2 * ni) return;
+    for (size_t i = 0; i < ni; i++) {
+        CHECK(g.hit_base[i] == g.DI[i].hit_base && g.hit_base[i] == s.instances[i].hit_base, "instance %zu: hit_base %d", i, g.hit_base[i]);
+        CHECK(g.hit_base[i] >= g.n_world && (i == 0 || g.hit_base[i] > g.hit_base[i - 1]), "instance %zu: hit_base %d not ascending", i,
+              g.hit_base[i]);
+        // its class: its rank by BLAS root, then index, scaled to 0..127
+        size_t rank = 0;
+        for (size_t j = 0; j < ni; j++) rank += g.DI[j].root < g.DI[i].root || (g.DI[j].root == g.DI[i].root && j < i);
+        CHECK(g.cls[i] == std::min<size_t>(127, rank * 128 / ni), "instance %zu: class %u at rank %zu of %zu", i, g.cls[i], rank, ni);
+        // its cell: the low corner of its own BLAS's box + the BLAS bit, 4 / extent
+        const size_t b = (size_t)s.instances[i].blas;
+        float lo[3], hi[3], tol;
+        blas_box(g, b, lo, hi, &tol);
+        const F4 c0 = g.cell[2 * i], c1 = g.cell[2 * i + 1];
+        const float got_lo[3] = {c0.x, c0.y, c0.z}, got_sc[3] = {c1.x, c1.y, c1.z};
+        for (int a = 0; a < 3; a++) {
+            const float ext = hi[a] - lo[a], want = 4.f / ext;
+            CHECK(ext > 100.f * tol, "BLAS %zu axis %d: extent %g", b, a, ext);
+            CHECK(fabsf(got_lo[a] - lo[a]) <= tol, "instance %zu axis %d: cell lo %.9g, BLAS %zu box lo %.9g (tol %g)", i, a, got_lo[a], b, lo[a], tol);
+            CHECK(fabsf(got_sc[a] - want) <= want * (2.f * tol / ext + 4.f * 1.1920929e-7f), "instance %zu axis %d: cell scale %.9g, 4 / extent %.9g", i,
+                  a, got_sc[a], want);
+        }
+        CHECK(c0.w == (float)(b & 1) && c1.w == 0.f, "instance %zu: BLAS bit %g of BLAS %zu, pad %g", i, c0.w, b, c1.w);
+    }
+}
+
+// the boxes of two BLASes lie further apart than the tolerance of the cell check, so a cell
+// taken from the wrong BLAS shows
+static void check_blases_differ(const DeviceImage& g) {
+    for (size_t b = 1; b < g.blas.size(); b++) {
+        float lo0[3], hi0[3], lo1[3], hi1[3], t0, t1;
+        blas_box(g, 0, lo0, hi0, &t0);
+        blas_box(g, b, lo1, hi1, &t1);
+        float far = 0.f;
+        for (int a = 0; a < 3; a++) far = std::max(far, std::max(fabsf(lo0[a] - lo1[a]), fabsf((hi0[a] - lo0[a]) - (hi1[a] - lo1[a]))));
+        CHECK(far > 1000.f * std::max(t0, t1), "BLAS 0 and %zu have the same box", b);
+    }
+}
+
 static void run(const char* name, Scene& s, size_t want_bytes) {
     g_scene = name;
     std::string err;
@@ -133,6 +203,8 @@ static void run(const char* name, Scene& s, size_t want_bytes) {
     DeviceImage g;
     must(build_image(s, g, err), err, "build_image");
     check_image(s, g, want_bytes);
+    check_bin_tables(s, g);
+    check_blases_differ(g);
     printf("%s: %zu nodes (%zu world), %zu packets, %zu instances, lds_ok %d, has_mb %d, %zu bytes\n", name, g.DN.size(),
            s.nodes.size(), g.DL.size(), g.DI.size(), (int)g.lds_ok, (int)g.has_mb, g.bytes);
 }
@@ -147,16 +219,22 @@ int main(int argc, char** argv) {
         add_obj(s, dir + "cornell_box.obj");
         run("cornell", s, strtoull(argv[2], nullptr, 10));
     }
-    {   // a world teapot and a BLAS of a second one with two instances: the renumbering is on
+    {   // a world teapot, a BLAS of a second one with two instances and, between them, one instance of
+        // a BLAS of the box (so the ray-bin tables can mix BLASes up): the renumbering is on
         Scene s;
         base_scene(s);
         add_obj(s, dir + "teapot.obj");
         const int32_t m = add_obj(s, dir + "teapot.obj");
         const int32_t b = make_blas(s, &m, 1, err);
         must(b, err, "make_blas");
+        const int32_t m2 = add_obj(s, dir + "cornell_box.obj");
+        const int32_t b2 = make_blas(s, &m2, 1, err);
+        must(b2, err, "make_blas");
         for (int i = 0; i < 2; i++) {
             const float m16[16] = {1, 0, 0, 4.f * (float)(i + 1), 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
             must(add_instance(s, b, m16, err), err, "add_instance");
+            const float box16[16] = {0, 0.5f, 0, -6, -0.5f, 0, 0, 1, 0, 0, 0.25f, 2, 0, 0, 0, 1};   // a quarter turn, scaled
+            if (i == 0) must(add_instance(s, b2, box16, err), err, "add_instance");
         }
         run("instanced", s, strtoull(argv[3], nullptr, 10));
     }

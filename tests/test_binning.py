@@ -91,6 +91,49 @@ def test_binned_chain_chunks_equal_one_chunk():
 
 
 @pytest.mark.gpu
+def test_binned_adaptive_chunks_equal_one_chunk():
+    """An adaptive pass through chunks of units with binning on: each chunk's shadow-ray batch
+    is bounded by the device's unit count less the chunk's first unit (csrc/mrt_device.hip,
+    the adaptive form of the count with a non-zero `sub`)."""
+    P, _, cam = CASES["adapt_pt_panel"]()
+    out = runs(P, cam, 70, 50, [dict(bin=0), dict(bin=6, chain_mb=1)])
+    assert_all_same(out)
+    assert out[1][2]["chain_chunks"] > 1, out[1][2]
+
+
+@pytest.mark.gpu
+def test_light_samples_on_instances_under_a_dome_are_the_same_binned():
+    """lightSamples on a small scene in the style of config C5 (two BLASes, nine instances on a
+    floor, a dome light) at the 37 x 29 points of tests/test_light_samples.py: unbinned, the
+    default, and with the instance-major and object-space keys asked for, every record, count
+    and sum has the same bits and the same rays are traced."""
+    from conftest import ref_model
+    from helpers import scene_pair
+    from miro import scenes
+    from test_light_samples import same
+    from test_sample_lights import H as PH, W as PW, blinn_frame
+    cfg = dict(scenes.CONFIGS["C5"], lights=[dict(type="dome", sky=(64, 32), power=0.15, samples=3, noise=0.001)],
+               env=dict(sky=(64, 32), exposure=1.0))
+    placed = [(i % 2, M) for i, M in enumerate(scenes.instance_transforms(n=9, grid=3, spacing=3.2, seed=64))]
+    P, _, cam = scene_pair(cfg, floor=True, instances=((ref_model("teapot.obj"), ref_model("sphere2.obj")), placed))
+    o, d, t = camera(dict(cam, eye=(0.0, 6.0, 14.0))).rays(PW, PH, 11)   # (nearer: the nine instances fill the frame)
+    hits = P.traceRays(o, d, t)
+    surf = P.hitSurfaces(o, d, hits)
+    assert (hits["inst"] >= 0).sum() > 50
+    n, rvec = blinn_frame(d, surf["n"], surf["geo_n"])
+    flat = lambda x: np.ascontiguousarray(x.reshape(-1, 3))
+    ref = rays = None
+    for knobs in (dict(bin=0), dict(), dict(bin=1, bin_inst=1), dict(bin=1, bin_inst=2)):
+        with tuned(**knobs):
+            got = P.lightSamples(flat(surf["p"]), flat(n), flat(rvec), time=np.ascontiguousarray(t.reshape(-1)), seed=7, e=True, per_light=True)
+            st = P.last_stats["shadow_rays"]
+        if ref is None:
+            ref, rays = got, st
+        assert same(got, ref) and st == rays > 0, knobs
+    assert np.any(ref["e"] > 0) and ref["counts"].sum() > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("case", ["pt_rect_panel", "pt_panel_env", "mixed_rect_point", "disp_cornell_mixed",
                                   "adapt_mixed_rect", "leaf_translucent"])
 def test_chain_trace_schedules_give_identical_frames(case):

@@ -1,12 +1,15 @@
 """The host image of a device replica (build_image, csrc/host_image.cpp) without a GPU:
 tests/native/device_image.cpp, built with g++ against the plain C++ host sources, builds three
 scenes -- the Cornell box (fewer than 64 world nodes: no LDS renumbering), a world teapot plus a
-BLAS of a second teapot with two instances (renumbered), a motion-blurred teapot beside the
-box -- and checks what every kernel relies on: child words, leaf words against their packets,
-slot kinds, the node permutation and its breadth-first head, BLAS roots, PrimShade indices,
-the time-1 vertices, and the byte total.  tests/golden/device_image_bytes.json holds
-mrt_scene_info.device_bytes of the same three scenes, recorded from an upload by the commit
-before build_image existed."""
+BLAS of a second teapot with two instances and a BLAS of the box with one between them
+(renumbered), a motion-blurred teapot beside the box -- and checks what every kernel relies on:
+child words, leaf words against their packets, slot kinds, the node permutation and its
+breadth-first head, BLAS roots, PrimShade indices, the time-1 vertices, the instance-major
+ray-bin tables (hit bases ascending, classes ranked by BLAS root then index, each instance's
+cell against the box of its own BLAS's packets), and the byte total.
+tests/golden/device_image_bytes.json holds mrt_scene_info.device_bytes of the same three
+scenes, recorded from an upload: the first and third by the commit before build_image existed,
+the instanced scene's when it got its second BLAS."""
 import json
 import os
 import shutil
